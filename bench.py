@@ -16,6 +16,13 @@ Contract (driver): python bench.py --gpus N --steps K --warmup W
   * W untimed warmup steps, then exactly K timed steps bracketed by
     barrier + torch.cuda.synchronize; MAX elapsed over ranks; rank 0
     prints ONE JSON line.
+  * --dump-outputs DIR writes what the last timed step produced (trained
+    weights, loss histories, anomaly thresholds, CV scores) as
+    DIR/<name>.npy so two builds of the project can be compared output
+    for output; the inputs are a pure function of the arguments.
+  * --full is reserved for measurements beyond the headline figure; a
+    plain run does only setup, warmup, the timed steps and the result
+    line. Today it adds the per-phase build ledger (as --verbose).
 """
 from __future__ import annotations
 
@@ -40,6 +47,7 @@ EPOCHS = 5
 BATCH_DENSE = 256
 BATCH_LSTM = 256
 MACHINES_PER_GPU = 125  # x8 GPUs = the 1000-machine config
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs budget over all arrays
 
 
 def make_machine_cfg(i: int, kind: str) -> dict:
@@ -94,6 +102,87 @@ def make_machine_cfg(i: int, kind: str) -> dict:
     return {"name": f"bench-{kind}-{i}", "model": model, "dataset": dataset}
 
 
+def _numeric_leaves(obj, out: list):
+    """Numeric leaves of a nested dict/list in sorted-key order."""
+    if isinstance(obj, dict):
+        for k in sorted(obj):
+            _numeric_leaves(obj[k], out)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            _numeric_leaves(v, out)
+    elif isinstance(obj, (int, float, np.integer, np.floating)) and not (
+        isinstance(obj, bool)
+    ):
+        out.append(float(obj))
+
+
+def _fit_dump_budget(arrays: dict, max_bytes: int) -> dict:
+    """Keep [n_machines, n] arrays within max_bytes in all: the small
+    ones stay whole; the weight matrices share what is left, sampled by
+    column with a fixed seed (the same columns in every run)."""
+    big = [k for k in arrays if k.startswith("weights_")]
+    left = max_bytes - sum(
+        a.nbytes for k, a in arrays.items() if k not in big
+    )
+    if sum(arrays[k].nbytes for k in big) <= left:
+        return arrays
+    out = dict(arrays)
+    rng = np.random.default_rng(0)
+    for k in big:
+        a = arrays[k]
+        keep = max(left, 0) // len(big) // (a.shape[0] * a.itemsize)
+        if keep < a.shape[1]:
+            cols = np.sort(rng.choice(a.shape[1], keep, replace=False))
+            out[k] = np.ascontiguousarray(a[:, cols])
+    return out
+
+
+def dump_outputs(dump_dir: str, results, model_dir: str, suffix: str = ""):
+    """Write what a caller of the timed build received in its last step:
+    per machine (config order) the saved model's trained weights, loss
+    history and DiffBased thresholds, and the CV scores of the returned
+    Machine metadata. One [n_machines, ...] array per quantity and model
+    kind; arrays that would exceed the budget keep a fixed seeded sample
+    of their columns."""
+    from gordo_amd import serializer
+    from gordo_amd.parallel.packed_builder import _classify
+
+    rows: dict = {}
+    for name, machine in results:
+        kind = "lstm" if "-lstm-" in name else "dense"
+        model = serializer.load(os.path.join(model_dir, name))
+        detector, _, inner = _classify(model)
+        weights = inner._weights
+        cv = machine.metadata.build_metadata.model.cross_validation
+        scores: list = []
+        _numeric_leaves(cv.scores, scores)
+        per_machine = {
+            f"weights_{kind}": np.concatenate(
+                [np.asarray(weights[k], np.float32).ravel()
+                 for k in sorted(weights)]
+            ),
+            f"loss_history_{kind}": np.asarray(
+                inner.history["loss"], np.float64
+            ),
+            f"feature_thresholds_{kind}": np.asarray(
+                detector.feature_thresholds_, np.float64
+            ).ravel(),
+            f"aggregate_threshold_{kind}": np.asarray(
+                [detector.aggregate_threshold_], np.float64
+            ),
+            f"cv_scores_{kind}": np.asarray(scores, np.float64),
+        }
+        for k, v in per_machine.items():
+            rows.setdefault(k, []).append(v)
+
+    arrays = _fit_dump_budget(
+        {k: np.stack(v) for k, v in rows.items()}, DUMP_BYTES_MAX
+    )
+    os.makedirs(dump_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dump_dir, f"{k}{suffix}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -102,7 +191,15 @@ def main():
     ap.add_argument("--machines-per-gpu", type=int, default=MACHINES_PER_GPU)
     ap.add_argument("--verbose", action="store_true",
                     help="log per-phase build timings to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what is not needed for the headline "
+                         "figure (today: the per-phase build ledger)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import logging
 
@@ -154,6 +251,7 @@ def main():
         if timed:
             for k, v in builder.phase_times.items():
                 phase_acc[k] = phase_acc.get(k, 0.0) + v
+        return results
 
     import torch.distributed as dist
 
@@ -169,7 +267,7 @@ def main():
     barrier_sync()
     t0 = time.time()
     for _ in range(args.steps):
-        one_step(timed=True)
+        last_results = one_step(timed=True)
     barrier_sync()
     elapsed = time.time() - t0
 
@@ -183,9 +281,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:
+        dump_outputs(
+            args.dump_outputs, last_results, out_dir,
+            suffix=f"_rank{rank}" if world > 1 else "",
+        )
+
     shutil.rmtree(out_dir, ignore_errors=True)
 
-    if rank == 0 and args.verbose:
+    if rank == 0 and (args.verbose or args.full):
         # per-step phase budget (seconds averaged over the timed steps;
         # 'total' is the sequential wall — overlapped keys are informational)
         budget = {k: round(v / args.steps, 3) for k, v in
