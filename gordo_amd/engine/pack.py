@@ -6,13 +6,17 @@ The MI355X-native answer to the reference's pod-per-model fan-out
 set of grouped tensors — weights ``[G, in, out]``, activations
 ``[G, B, F]`` — so every layer of every model in the pack is a single
 grouped MFMA GEMM launch instead of thousands of tiny ones. Per-model
-data, per-model losses, per-model Adam state; one flat fp32 parameter
-buffer (+ bf16 compute mirror on GPU) per pack so the optimizer is one
-fused kernel over the whole fleet shard.
+data, per-model losses, per-model optimizer state; one flat fp32
+parameter buffer (+ bf16 compute mirror on GPU) per pack so the
+optimizer is one fused kernel over the whole fleet shard.
 
-Training math matches Keras defaults (glorot-uniform kernels,
-orthogonal LSTM recurrent kernels, unit forget-gate bias, Adam with
-bias correction, MSE loss) — reference factories:
+Training math matches Keras (glorot-uniform kernels, orthogonal LSTM
+recurrent kernels, unit forget-gate bias) and honours the spec's
+compile settings: the loss is one of mse / mae / huber / logcosh
+(``ops.loss_bwd``, which also counts the Keras ``accuracy`` metric) and
+the optimizer one of Adam (+amsgrad) / SGD / RMSprop / Adagrad / Adamax
+with Keras 3 defaults (``ops.optimizer_step``). The default is Adam with
+bias correction and MSE — reference factories:
 gordo/machine/model/factories/feedforward_autoencoder.py,
 lstm_autoencoder.py.
 """
@@ -47,9 +51,12 @@ def pad_enabled(device) -> bool:
     bf16 staging is a 2-2.5x tax), and padded hidden units are
     PROVABLY inert: zero weights + zero bias give g=tanh(0)=0 so
     c=f*0+i*0=0 and h=o*tanh(0)=0 forever; all their gradients are
-    exactly 0 (dc=dh=0 chains), so Adam keeps their weights at 0.
-    Only the MSE mean needs the REAL element count (ops.mse_bwd
-    real_n). CPU packs stay unpadded (they are the fp32 oracle)."""
+    exactly 0 (dc=dh=0 chains), so every supported optimizer keeps
+    their weights at 0 (each update is a multiple of g or of a moment
+    of g). Every supported loss is 0 with zero gradient at d=0, so pad
+    output columns add nothing; only the mean needs the REAL element
+    count (ops.loss_bwd real_f). CPU packs stay unpadded (they are the
+    fp32 oracle)."""
     return (
         torch.device(device).type == "cuda"
         and os.environ.get("GORDO_PAD8", "1") != "0"
@@ -73,11 +80,23 @@ def _orthogonal(shape, gen):
 
 
 class _ParamStore:
-    """One flat fp32 master buffer + grads + Adam state (+ bf16 compute
-    mirror on GPU), carved into named [G, ...] views."""
+    """One flat fp32 master buffer + grads + optimizer state (+ bf16
+    compute mirror on GPU), carved into named [G, ...] views.
 
-    def __init__(self, device: torch.device):
+    The state slots keep their Adam names: ``m`` is slot 0 (Adam/Adamax
+    first moment, SGD momentum, RMSprop mean square, Adagrad
+    accumulator), ``v`` slot 1 (Adam second moment, Adamax infinity
+    norm, RMSprop momentum); ``vhat`` exists only for Adam+amsgrad."""
+
+    def __init__(self, device: torch.device, optimizer_kind: str = "adam",
+                 optimizer_params: Optional[Dict[str, Any]] = None):
         self.device = device
+        self.optimizer_kind = optimizer_kind
+        if optimizer_params is None:
+            from .spec import resolve_optimizer
+
+            optimizer_params = resolve_optimizer(optimizer_kind)[1]
+        self.optimizer_params = dict(optimizer_params)
         self.compute_dtype = _compute_dtype(device)
         self._shapes: List[Tuple[str, Tuple[int, ...]]] = []
         self.logical: Dict[str, Tuple[int, ...]] = {}
@@ -102,12 +121,19 @@ class _ParamStore:
         self.g32 = torch.zeros(self._total, dtype=torch.float32, device=dev)
         self.m = torch.zeros(self._total, dtype=torch.float32, device=dev)
         self.v = torch.zeros(self._total, dtype=torch.float32, device=dev)
+        self.vhat = (
+            torch.zeros(self._total, dtype=torch.float32, device=dev)
+            if self.optimizer_kind == "adam"
+            and self.optimizer_params.get("amsgrad")
+            else None
+        )
+        self._init_slots()
         self.plp = (
             torch.zeros(self._total, dtype=self.compute_dtype, device=dev)
             if self.compute_dtype != torch.float32
             else None
         )
-        # device-resident Adam step counter (hipGraph-capturable)
+        # device-resident optimizer step counter (hipGraph-capturable)
         self.step_buf = (
             torch.zeros(1, dtype=torch.int32, device=dev)
             if dev.type == "cuda"
@@ -138,9 +164,36 @@ class _ParamStore:
             step_buf=self.step_buf,
         )
 
-    def reset_adam(self):
-        self.m.zero_()
+    def optimizer_step(self):
+        """One step of the spec's optimizer over the whole buffer."""
+        self.step_count += 1
+        ops.optimizer_step(
+            self.optimizer_kind, self.p32, self.g32, self.m, self.v,
+            self.vhat, self.optimizer_params, self.step_count, self.plp,
+            step_buf=self.step_buf,
+        )
+
+    def _init_slots(self):
+        if self.optimizer_kind == "adagrad":
+            self.m.fill_(
+                float(self.optimizer_params["initial_accumulator_value"])
+            )
+        else:
+            self.m.zero_()
         self.v.zero_()
+        if self.vhat is not None:
+            self.vhat.zero_()
+
+    def slots(self) -> List[Tuple[str, torch.Tensor]]:
+        """(key prefix, flat state tensor) for every slot that exists."""
+        out = [("m", self.m), ("v", self.v)]
+        if self.vhat is not None:
+            out.append(("vhat", self.vhat))
+        return out
+
+    def reset_adam(self):
+        """Reset the optimizer state (whatever the optimizer)."""
+        self._init_slots()
         self.step_count = 0
         if self.step_buf is not None:
             self.step_buf.zero_()
@@ -155,7 +208,13 @@ class BasePack:
             device if device is not None else
             ("cuda" if torch.cuda.is_available() else "cpu")
         )
-        self.store = _ParamStore(self.device)
+        self.store = _ParamStore(
+            self.device, spec.optimizer_kind, spec.optimizer_params
+        )
+        self._loss_kind = spec.loss_kind
+        self._loss_delta = float(spec.loss_params.get("delta", 1.0))
+        # per-model Keras "accuracy" hit count of the latest train_batch
+        self.last_correct: Optional[torch.Tensor] = None
         self.pad8 = pad_enabled(self.device)
         self._pad = _pad8 if self.pad8 else (lambda n: int(n))
         # per-param custom logical<->physical converters (LSTM gate
@@ -186,10 +245,23 @@ class BasePack:
     def train_batch(self, Xb, Tb) -> torch.Tensor:
         raise NotImplementedError
 
-    def eval_batch(self, Xb, Tb) -> torch.Tensor:
-        """Forward-only per-model loss for a gathered batch (the
-        validation pass of fit)."""
+    def eval_batch_stats(self, Xb, Tb) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Forward-only (per-model configured loss, accuracy hit count)
+        for a gathered batch (the validation pass of fit)."""
         raise NotImplementedError
+
+    def eval_batch(self, Xb, Tb) -> torch.Tensor:
+        """Forward-only per-model loss for a gathered batch."""
+        return self.eval_batch_stats(Xb, Tb)[0]
+
+    def _loss_bwd(self, Y, Tb, want_grad: bool = True):
+        """The spec's loss over [G, B, F_physical] outputs/targets:
+        (loss[G], dY | None, correct[G]); means divide by the LOGICAL
+        width (pad diffs are exactly 0 and every loss is 0 at 0)."""
+        return ops.loss_bwd(
+            Y, Tb.to(Y.dtype), self._loss_kind, self._logical_out,
+            self._loss_delta, want_grad,
+        )
 
     # -- common ----------------------------------------------------------
     @property
@@ -280,12 +352,10 @@ class BasePack:
         for name in self.param_names():
             off, n = self.store._offsets[name]
             shape = self.store.views[name].shape
-            out["m:" + name] = (
-                self.store.m[off : off + n].view(*shape)[g].cpu().numpy().copy()
-            )
-            out["v:" + name] = (
-                self.store.v[off : off + n].view(*shape)[g].cpu().numpy().copy()
-            )
+            for prefix, slot in self.store.slots():
+                out[prefix + ":" + name] = (
+                    slot[off : off + n].view(*shape)[g].cpu().numpy().copy()
+                )
         return out
 
     # ---- the epoch loop ------------------------------------------------
@@ -343,7 +413,8 @@ class BasePack:
                 # capture does not perturb the training trajectory.
                 store = self.store
                 snap = (
-                    store.p32.clone(), store.m.clone(), store.v.clone(),
+                    store.p32.clone(),
+                    [slot.clone() for _k, slot in store.slots()],
                     store.step_buf.clone(), store.step_count,
                 )
                 with BasePack._graph_capture_lock:
@@ -359,13 +430,14 @@ class BasePack:
                         graph, capture_error_mode="thread_local"
                     ):
                         loss = self.train_batch(sx, st)
+                        correct = self.last_correct
                 store.p32.copy_(snap[0])
-                store.m.copy_(snap[1])
-                store.v.copy_(snap[2])
-                store.step_buf.copy_(snap[3])
-                store.step_count = snap[4]
+                for (_k, slot), saved in zip(store.slots(), snap[1]):
+                    slot.copy_(saved)
+                store.step_buf.copy_(snap[2])
+                store.step_count = snap[3]
                 store.sync_lp()
-                entry = cached[key] = (graph, sx, st, loss)
+                entry = cached[key] = (graph, sx, st, loss, correct)
             except Exception:
                 logger.warning(
                     "hipGraph capture failed; falling back to eager",
@@ -373,11 +445,12 @@ class BasePack:
                 )
                 self._graph_enabled = False
                 return None
-        graph, sx, st, loss = entry
+        graph, sx, st, loss, correct = entry
         sx.copy_(Xb)
         st.copy_(Tb)
         graph.replay()
         self.store.step_count += 1  # device step_buf is the truth
+        self.last_correct = correct
         return loss
 
     def release_graphs(self):
@@ -465,13 +538,15 @@ class BasePack:
         Train the whole pack. X: [G, N, F_in] (already on device),
         Y: [G, N, F_out]. Returns a Keras-style history dict with
         per-model per-epoch values: {"loss": [[...G...] per epoch],
-        "accuracy": ...}.
+        "accuracy": ...}. ``loss`` is the spec's configured loss and
+        ``accuracy`` the Keras metric of that name (argmax agreement
+        per row; binary accuracy for one output column), accumulated
+        over the epoch's batches as Keras does.
         """
         if self.pad8:
             X = self._pad_features(X, self._logical_in)
             Y = self._pad_features(Y, self._logical_out)
         G, N = X.shape[0], X.shape[1]
-        adam = self.spec.adam_params
         history: Dict[str, list] = {"loss": [], "accuracy": []}
         n_all = self._n_samples(N)
         # keras validation_split semantics: the LAST fraction of samples
@@ -510,6 +585,9 @@ class BasePack:
                     .expand(G, -1)
                 )
             epoch_loss = torch.zeros(G, dtype=torch.float32, device=self.device)
+            epoch_correct = torch.zeros(
+                G, dtype=torch.float32, device=self.device
+            )
             samples_seen = 0
             for b in range(n_batches):
                 idx = perm[:, b * batch_size : (b + 1) * batch_size]
@@ -520,12 +598,20 @@ class BasePack:
                 if loss is None:
                     loss = self.train_batch(Xb, Tb)
                 epoch_loss += loss * idx.shape[1]
+                epoch_correct += self.last_correct
                 samples_seen += idx.shape[1]
-            epoch_loss = (epoch_loss / max(samples_seen, 1)).cpu().tolist()
+            # loss and accuracy leave the device together: one transfer
+            epoch_stats = torch.stack(
+                [epoch_loss, epoch_correct]
+            ) / max(samples_seen, 1)
+            epoch_loss, epoch_acc = epoch_stats.cpu().tolist()
             history["loss"].append(epoch_loss)
-            history["accuracy"].append([0.0] * G)
+            history["accuracy"].append(epoch_acc)
             if n_val > 0:
                 val_loss = torch.zeros(G, dtype=torch.float32, device=self.device)
+                val_correct = torch.zeros(
+                    G, dtype=torch.float32, device=self.device
+                )
                 vseen = 0
                 for vs_ in range(n_train, n_all, batch_size):
                     vidx = (
@@ -534,11 +620,15 @@ class BasePack:
                         ).unsqueeze(0).expand(G, -1)
                     )
                     Xvb, Tvb = self._gather_batch(X, Y, vidx)
-                    val_loss += self.eval_batch(Xvb, Tvb) * vidx.shape[1]
+                    vl, vc = self.eval_batch_stats(Xvb, Tvb)
+                    val_loss += vl * vidx.shape[1]
+                    val_correct += vc
                     vseen += vidx.shape[1]
-                val_losses = (val_loss / max(vseen, 1)).cpu().tolist()
+                val_losses, val_acc = (
+                    torch.stack([val_loss, val_correct]) / max(vseen, 1)
+                ).cpu().tolist()
                 history["val_loss"].append(val_losses)
-                history["val_accuracy"].append([0.0] * G)
+                history["val_accuracy"].append(val_acc)
             if verbose:
                 logger.info(
                     "epoch %d/%d mean-loss=%.6g", epoch + 1, epochs,
@@ -626,20 +716,17 @@ class DensePack(BasePack):
         out = self.forward(Xc)[-1]
         return out[..., : self._logical_out]
 
-    def eval_batch(self, Xb, Tb) -> torch.Tensor:
-        # pad diffs are exactly 0; divide by the REAL element count
+    def eval_batch_stats(self, Xb, Tb):
         Xb, Tb = self._pad_io(Xb, Tb)
-        out = self.forward(Xb)[-1].float()
-        n = Xb.shape[1] * self._logical_out
-        return ((out - Tb.float()) ** 2).sum(dim=(1, 2)) / n
+        loss, _, correct = self._loss_bwd(
+            self.forward(Xb)[-1], Tb, want_grad=False
+        )
+        return loss, correct
 
     def train_batch(self, Xb, Tb) -> torch.Tensor:
         Xb, Tb = self._pad_io(Xb, Tb)
         acts = self.forward(Xb)
-        loss, dA = ops.mse_bwd(
-            acts[-1], Tb.to(acts[-1].dtype),
-            Xb.shape[1] * self._logical_out,
-        )
+        loss, dA, self.last_correct = self._loss_bwd(acts[-1], Tb)
         for i in range(len(self.layer_meta) - 1, -1, -1):
             _fin, _fout, act, l1 = self.layer_meta[i]
             dZ = ops.act_l1_bwd(dA, acts[i + 1], act, l1)
@@ -648,8 +735,7 @@ class DensePack(BasePack):
             self.store.gviews[f"b{i}"].copy_(db)
             if i > 0:
                 dA = ops.grouped_linear_bwd_data(dZ, self.store.cviews[f"W{i}"])
-        a = self.spec.adam_params
-        self.store.adam_step(a["lr"], a["beta1"], a["beta2"], a["eps"])
+        self.store.optimizer_step()
         return loss
 
 
@@ -891,19 +977,16 @@ class LSTMPack(BasePack):
         y, _ = self._forward_seq(Xc, keep=False)
         return y[..., : self._logical_out]
 
-    def eval_batch(self, Xw, Tb) -> torch.Tensor:
+    def eval_batch_stats(self, Xw, Tb):
         Xw, Tb = self._pad_io(Xw, Tb)
-        y = self.predict_windows(Xw).float()
-        return (
-            (y - Tb.float()[..., : self._logical_out]) ** 2
-        ).mean(dim=(1, 2))
+        y, _ = self._forward_seq(self._to_compute(Xw), keep=False)
+        loss, _, correct = self._loss_bwd(y, Tb, want_grad=False)
+        return loss, correct
 
     def _train_batch_fused(self, Xw, Tb) -> torch.Tensor:
         G, B, T, _ = Xw.shape
         y, cache = self._forward_seq_fused(Xw, keep=True)
-        loss, dY = ops.mse_bwd(
-            y, Tb.to(y.dtype), B * self._logical_out
-        )
+        loss, dY, self.last_correct = self._loss_bwd(y, Tb)
 
         fin, fout, act = self.dense_meta
         head = cache[-1]
@@ -961,8 +1044,7 @@ class LSTMPack(BasePack):
                 )
             del dG_flat, prev_dSeq
 
-        a = self.spec.adam_params
-        self.store.adam_step(a["lr"], a["beta1"], a["beta2"], a["eps"])
+        self.store.optimizer_step()
         return loss
 
     def train_batch(self, Xw, Tb) -> torch.Tensor:
@@ -971,9 +1053,7 @@ class LSTMPack(BasePack):
             return self._train_batch_fused(Xw, Tb)
         G, B, T, _ = Xw.shape
         y, cache = self._forward_seq(Xw, keep=True)
-        loss, dY = ops.mse_bwd(
-            y, Tb.to(y.dtype), B * self._logical_out
-        )
+        loss, dY, self.last_correct = self._loss_bwd(y, Tb)
 
         # output dense layer backward
         fin, fout, act = self.dense_meta
@@ -1026,8 +1106,7 @@ class LSTMPack(BasePack):
             if li > 0:
                 dSeq = ops.grouped_linear_bwd_data(dG_flat, Wx).view(G, B, T, fin)
 
-        a = self.spec.adam_params
-        self.store.adam_step(a["lr"], a["beta1"], a["beta2"], a["eps"])
+        self.store.optimizer_step()
         return loss
 
     # ---- windowed fit/predict over a series ---------------------------

@@ -9,7 +9,176 @@ lstm_autoencoder.py) produce these specs; the packed engine
 from __future__ import annotations
 
 from dataclasses import dataclass, field, asdict
-from typing import Any, Dict, List
+from typing import Any, Dict, List, Optional, Tuple
+
+
+# ---- compile settings -------------------------------------------------
+# Keras names and aliases (case-insensitive) -> the engine's canonical
+# loss / optimizer names. Anything else raises: a silent fallback to
+# Adam/MSE would train a different model than the one configured.
+_LOSS_ALIASES = {
+    "mse": "mse",
+    "mean_squared_error": "mse",
+    "meansquarederror": "mse",
+    "mae": "mae",
+    "mean_absolute_error": "mae",
+    "meanabsoluteerror": "mae",
+    "huber": "huber",
+    "huber_loss": "huber",
+    "logcosh": "logcosh",
+    "log_cosh": "logcosh",
+}
+_LOSS_KWARGS = {"huber": {"delta": 1.0}}
+
+# per-optimizer hyperparameters and their Keras 3 defaults
+_OPTIMIZER_DEFAULTS: Dict[str, Dict[str, Any]] = {
+    "adam": dict(learning_rate=0.001, beta_1=0.9, beta_2=0.999,
+                 epsilon=1e-7, amsgrad=False),
+    "sgd": dict(learning_rate=0.01, momentum=0.0, nesterov=False),
+    "rmsprop": dict(learning_rate=0.001, rho=0.9, momentum=0.0,
+                    epsilon=1e-7),
+    "adagrad": dict(learning_rate=0.001, initial_accumulator_value=0.1,
+                    epsilon=1e-7),
+    "adamax": dict(learning_rate=0.001, beta_1=0.9, beta_2=0.999,
+                   epsilon=1e-7),
+}
+
+
+def _is_off(v: Any) -> bool:
+    """Keras optimizer kwargs the engine has no analog for are accepted
+    only at their "off" value: None or False themselves (identity — 0
+    and 0.0 compare equal to False but are settings, so they raise)."""
+    return v is None or v is False
+
+
+def normalize_loss(name: Any) -> str:
+    """Canonical loss name (``mse``/``mae``/``huber``/``logcosh``).
+
+    >>> normalize_loss("mean_squared_error"), normalize_loss("Huber")
+    ('mse', 'huber')
+    """
+    key = str(name).rsplit(".", 1)[-1].lower() if isinstance(name, str) else None
+    if key not in _LOSS_ALIASES:
+        raise ValueError(
+            f"Unsupported loss {name!r}; supported: "
+            f"{sorted(set(_LOSS_ALIASES.values()))}"
+        )
+    return _LOSS_ALIASES[key]
+
+
+def normalize_optimizer(name: Any) -> str:
+    """Canonical optimizer name.
+
+    >>> normalize_optimizer("Adam"), normalize_optimizer("RMSprop")
+    ('adam', 'rmsprop')
+    """
+    key = str(name).rsplit(".", 1)[-1].lower() if isinstance(name, str) else None
+    if key not in _OPTIMIZER_DEFAULTS:
+        raise ValueError(
+            f"Unsupported optimizer {name!r}; supported: "
+            f"{sorted(_OPTIMIZER_DEFAULTS)}"
+        )
+    return key
+
+
+def resolve_loss(loss: Any, loss_kwargs: Optional[Dict[str, Any]] = None
+                 ) -> Tuple[str, Dict[str, float]]:
+    """(canonical loss, complete kwargs) — raises ValueError on an
+    unknown loss or an unknown loss kwarg."""
+    kind = normalize_loss(loss)
+    params = dict(_LOSS_KWARGS.get(kind, {}))
+    for k, v in (loss_kwargs or {}).items():
+        if k in ("name", "reduction"):
+            if k == "reduction" and v not in (None, "sum_over_batch_size",
+                                              "auto"):
+                raise ValueError(f"Unsupported loss kwarg reduction={v!r}")
+            continue
+        if k not in params:
+            raise ValueError(f"Unsupported kwarg {k!r} for loss {loss!r}")
+        params[k] = float(v)
+    if kind == "huber" and not params["delta"] > 0.0:
+        raise ValueError(f"huber delta must be > 0, got {params['delta']!r}")
+    return kind, params
+
+
+def resolve_optimizer(optimizer: Any,
+                      optimizer_kwargs: Optional[Dict[str, Any]] = None
+                      ) -> Tuple[str, Dict[str, Any]]:
+    """(canonical optimizer, complete hyperparameters) with Keras 3
+    defaults filled in — raises ValueError naming the first kwarg the
+    engine cannot honour (clipnorm, weight_decay, centered=True, ...)."""
+    kind = normalize_optimizer(optimizer)
+    params = dict(_OPTIMIZER_DEFAULTS[kind])
+    for k, v in (optimizer_kwargs or {}).items():
+        if k == "name":
+            continue
+        if k == "lr":
+            k = "learning_rate"
+        if k not in params:
+            if _is_off(v):
+                continue  # e.g. centered=False, clipnorm=None
+            raise ValueError(
+                f"Unsupported optimizer kwarg {k!r} for {optimizer!r}"
+            )
+        if isinstance(params[k], bool):
+            if not isinstance(v, (bool, int)) or v not in (0, 1):
+                raise ValueError(
+                    f"Unsupported value for optimizer flag {k!r}: {v!r}"
+                )
+            params[k] = bool(v)
+        else:
+            if isinstance(v, (dict, list, tuple, str)) or v is None:
+                raise ValueError(
+                    f"Unsupported value for optimizer kwarg {k!r}: {v!r}"
+                )
+            params[k] = float(v)
+    return kind, params
+
+
+def parse_compile_kwargs(compile_kwargs: Optional[Dict[str, Any]]
+                         ) -> Tuple[str, Dict[str, Any]]:
+    """The factories' ``compile_kwargs``: returns (loss, loss_kwargs),
+    the loss name as the user wrote it. ``loss`` is a string or a
+    single-key dict with kwargs; ``metrics`` may only ask for accuracy
+    (history always carries it)."""
+    ck = dict(compile_kwargs or {})
+    loss = ck.pop("loss", None)
+    loss_kwargs: Dict[str, Any] = {}
+    if loss is None:
+        loss = "mse"
+    elif isinstance(loss, dict) and len(loss) == 1:
+        key = next(iter(loss))
+        loss_kwargs = dict(loss[key] or {})
+        loss = str(key).rsplit(".", 1)[-1]
+    elif not isinstance(loss, str):
+        raise ValueError(f"Unparsable compile entry loss={loss!r}")
+    metrics = ck.pop("metrics", None)
+    if isinstance(metrics, str):
+        metrics = [metrics]
+    for m in metrics or []:
+        if not (isinstance(m, str) and m.lower() in ("accuracy", "acc")):
+            raise ValueError(
+                f"Unsupported metrics entry {m!r}; only 'accuracy' is "
+                "computed by the engine"
+            )
+    for k, v in ck.items():
+        # settings that do not change the trained model pass through
+        if k in ("run_eagerly", "steps_per_execution", "jit_compile",
+                 "auto_scale_loss"):
+            continue
+        if v is None:
+            continue
+        raise ValueError(f"Unsupported compile kwarg {k!r}")
+    resolve_loss(loss, loss_kwargs)
+    return loss, loss_kwargs
+
+
+def _freeze(v: Any) -> Any:
+    if isinstance(v, dict):
+        return tuple(sorted((k, _freeze(x)) for k, x in v.items()))
+    if isinstance(v, (list, tuple)):
+        return tuple(_freeze(x) for x in v)
+    return v
 
 
 @dataclass
@@ -39,9 +208,27 @@ class ModelSpec:
     loss: str = "mse"
     optimizer: str = "Adam"
     optimizer_kwargs: Dict[str, Any] = field(default_factory=dict)
+    loss_kwargs: Dict[str, Any] = field(default_factory=dict)
+
+    def __post_init__(self):
+        # unsupported compile settings fail HERE, when the spec is
+        # built, before any device work. The stored loss/optimizer
+        # strings stay exactly as the user wrote them.
+        self.optimizer_kwargs = dict(self.optimizer_kwargs or {})
+        self.loss_kwargs = dict(self.loss_kwargs or {})
+        resolve_loss(self.loss, self.loss_kwargs)
+        resolve_optimizer(self.optimizer, self.optimizer_kwargs)
+
+    def __setstate__(self, state):
+        # specs pickled inside estimators saved before ``loss_kwargs``
+        # existed restore without it (unpickling bypasses __init__)
+        self.__dict__.update(state)
+        self.__dict__.setdefault("loss_kwargs", {})
 
     def to_dict(self) -> Dict[str, Any]:
         d = asdict(self)
+        if not d["loss_kwargs"]:
+            del d["loss_kwargs"]
         return d
 
     @classmethod
@@ -74,10 +261,32 @@ class ModelSpec:
             ),
             self.lookback_window,
             self.lookahead,
-            self.loss,
-            self.optimizer,
-            tuple(sorted(self.optimizer_kwargs.items())),
+            # normalised, defaults filled in: "adam"/"Adam" and
+            # "mse"/"mean_squared_error" share a pack
+            self.loss_kind,
+            _freeze(self.loss_params),
+            self.optimizer_kind,
+            _freeze(self.optimizer_params),
         )
+
+    # ---- compile settings (normalised) ---------------------------------
+    @property
+    def loss_kind(self) -> str:
+        return normalize_loss(self.loss)
+
+    @property
+    def loss_params(self) -> Dict[str, float]:
+        return resolve_loss(self.loss, self.loss_kwargs)[1]
+
+    @property
+    def optimizer_kind(self) -> str:
+        return normalize_optimizer(self.optimizer)
+
+    @property
+    def optimizer_params(self) -> Dict[str, Any]:
+        """Complete hyperparameters of the configured optimizer (Keras
+        3 defaults filled in, ``lr`` folded into ``learning_rate``)."""
+        return resolve_optimizer(self.optimizer, self.optimizer_kwargs)[1]
 
     @property
     def adam_params(self):

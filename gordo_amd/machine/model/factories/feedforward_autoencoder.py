@@ -7,7 +7,9 @@ engine ``ModelSpec`` consumed by the grouped MFMA device engine
 (engine/pack.DensePack) instead of a Keras graph. Semantics kept:
 encoder/decoder dims+activations, l1(1e-4) activity regularizer on
 every encoder layer except the first (reference :81), linear output
-layer, MSE loss, Adam.
+layer. ``optimizer``/``optimizer_kwargs`` and ``compile_kwargs`` (loss,
+metrics) are honoured as configured — default Adam + MSE; settings the
+engine cannot run raise ``ValueError`` (engine/spec.py).
 """
 from __future__ import annotations
 
@@ -15,7 +17,7 @@ from typing import Any, Dict, Optional, Tuple
 
 from ..register import register_model_builder
 from .utils import check_dim_func_len, hourglass_calc_dims
-from ....engine.spec import LayerSpec, ModelSpec
+from ....engine.spec import LayerSpec, ModelSpec, parse_compile_kwargs
 
 L1_ACTIVITY = 10e-5  # the reference's regularizers.l1(10e-5)
 
@@ -43,10 +45,16 @@ def feedforward_model(
     [8, 5, 5, 8, 10]
     >>> [l.l1_activity for l in spec.layers]
     [0.0, 0.0001, 0.0, 0.0, 0.0]
+    >>> spec = feedforward_model(10, optimizer="SGD",
+    ...                          compile_kwargs={"loss": {"Huber": {"delta": 0.5}}})
+    >>> spec.optimizer_kind, spec.loss_kind, spec.loss_params
+    ('sgd', 'huber', {'delta': 0.5})
     """
     n_features_out = n_features_out or n_features
     check_dim_func_len("encoding", encoding_dim, encoding_func)
     check_dim_func_len("decoding", decoding_dim, decoding_func)
+    # compile settings: loss (+kwargs) and metrics; unsupported ones raise
+    loss, loss_kwargs = parse_compile_kwargs(compile_kwargs)
 
     layers = []
     for i, (units, activation) in enumerate(zip(encoding_dim, encoding_func)):
@@ -67,8 +75,9 @@ def feedforward_model(
         n_features=int(n_features),
         n_features_out=int(n_features_out),
         layers=layers,
-        loss="mse",
-        optimizer=optimizer if isinstance(optimizer, str) else "Adam",
+        loss=loss,
+        loss_kwargs=loss_kwargs,
+        optimizer=optimizer,
         optimizer_kwargs=dict(optimizer_kwargs or {}),
     )
 

@@ -6,7 +6,8 @@ Mirror of the reference Keras builders
 engine ``ModelSpec`` consumed by the grouped LSTM device engine
 (engine/pack.LSTMPack). Semantics kept: stacked LSTM encoder with
 return_sequences=True, decoder whose LAST layer has
-return_sequences=False, Dense output layer, loss=mse, Adam.
+return_sequences=False, Dense output layer. The configured optimizer
+and ``compile_kwargs`` (loss, metrics) are honoured — default Adam + MSE.
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ from typing import Any, Dict, Optional, Tuple
 
 from ..register import register_model_builder
 from .utils import check_dim_func_len, hourglass_calc_dims
-from ....engine.spec import LayerSpec, ModelSpec
+from ....engine.spec import LayerSpec, ModelSpec, parse_compile_kwargs
 
 
 @register_model_builder(type="KerasLSTMAutoEncoder")
@@ -43,6 +44,8 @@ def lstm_model(
     n_features_out = n_features_out or n_features
     check_dim_func_len("encoding", encoding_dim, encoding_func)
     check_dim_func_len("decoding", decoding_dim, decoding_func)
+    # compile settings: loss (+kwargs) and metrics; unsupported ones raise
+    loss, loss_kwargs = parse_compile_kwargs(compile_kwargs)
 
     layers = []
     for units, activation in zip(encoding_dim, encoding_func):
@@ -72,8 +75,9 @@ def lstm_model(
         n_features_out=int(n_features_out),
         layers=layers,
         lookback_window=int(lookback_window),
-        loss="mse",
-        optimizer=optimizer if isinstance(optimizer, str) else "Adam",
+        loss=loss,
+        loss_kwargs=loss_kwargs,
+        optimizer=optimizer,
         optimizer_kwargs=dict(optimizer_kwargs or {}),
     )
 

@@ -26,7 +26,7 @@ from .base import GordoBase
 from .register import register_model_builder
 from ...core.import_utils import import_location
 from ...engine.pack import DensePack, LSTMPack
-from ...engine.spec import LayerSpec, ModelSpec
+from ...engine.spec import LayerSpec, ModelSpec, parse_compile_kwargs
 
 logger = logging.getLogger(__name__)
 
@@ -407,7 +407,8 @@ def _parse_raw_compile(compile_def: dict):
     OR nested single-key dicts with kwargs (reference
     models.py:401-460 passes the compile dict straight to keras, e.g.
     ``optimizer: {tensorflow.keras.optimizers.Adam: {learning_rate:
-    0.01}}``). Returns (loss, optimizer, optimizer_kwargs)."""
+    0.01}}``). Returns (loss, loss_kwargs, optimizer,
+    optimizer_kwargs); ``metrics`` may only ask for accuracy."""
     def _flatten(v, default):
         if v is None:
             return default, {}
@@ -419,12 +420,17 @@ def _parse_raw_compile(compile_def: dict):
             return key.rsplit(".", 1)[-1], kw
         raise ValueError(f"Unparsable compile entry {v!r}")
 
-    loss, _ = _flatten(compile_def.get("loss"), "mse")
+    loss, loss_kw = _flatten(compile_def.get("loss"), "mse")
     optimizer, opt_kw = _flatten(compile_def.get("optimizer"), "adam")
     # keras aliases: learning_rate/lr both seen in the wild
     if "learning_rate" in opt_kw:
         opt_kw["lr"] = opt_kw.pop("learning_rate")
-    return loss, optimizer, opt_kw
+    # metrics and the remaining compile keys: validated, not dropped
+    parse_compile_kwargs(
+        {k: v for k, v in compile_def.items()
+         if k not in ("loss", "optimizer")}
+    )
+    return loss, loss_kw, optimizer, opt_kw
 
 
 def _parse_raw_spec(
@@ -481,7 +487,7 @@ def _parse_raw_spec(
             )
     if not layers:
         raise ValueError("raw spec contains no layers")
-    loss, optimizer, opt_kw = _parse_raw_compile(compile_def or {})
+    loss, loss_kw, optimizer, opt_kw = _parse_raw_compile(compile_def or {})
     if has_lstm:
         if layers[-1].kind != "dense" or any(
             l.kind != "lstm" for l in layers[:-1]
@@ -500,6 +506,7 @@ def _parse_raw_spec(
             layers=layers,
             lookback_window=lookback_window,
             loss=loss,
+            loss_kwargs=loss_kw,
             optimizer=optimizer,
             optimizer_kwargs=opt_kw,
         )
@@ -509,6 +516,7 @@ def _parse_raw_spec(
         n_features_out=layers[-1].units,
         layers=layers,
         loss=loss,
+        loss_kwargs=loss_kw,
         optimizer=optimizer,
         optimizer_kwargs=opt_kw,
     )

@@ -151,6 +151,67 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, p_lp=None,
     return ref.adam_step(p, g, m, v, lr, beta1, beta2, eps, step, p_lp)
 
 
+def loss_bwd(Y, T, loss, real_f: int, delta: float = 1.0,
+             want_grad: bool = True):
+    """Per-model loss + grad + accuracy count in one pass over (Y, T):
+    ``(loss[G] f32, dY | None, correct[G] int32)``. ``loss`` is a
+    canonical name (mse/mae/huber/logcosh); ``real_f`` the logical
+    feature width when the last dim carries zero padding."""
+    kind = ref.loss_code(loss)
+    if _on_gpu(Y):
+        out = _require_hip().loss_bwd(
+            Y, T, kind, int(real_f), float(delta), bool(want_grad)
+        )
+        return out[0], out[1], out[2]
+    return ref.loss_bwd(Y, T, kind, int(real_f), float(delta), want_grad)
+
+
+# optimizer codes of train_ops.hip (plain Adam keeps adam_kernel)
+_OPT_SGD, _OPT_RMSPROP, _OPT_ADAGRAD, _OPT_ADAM_AMSGRAD, _OPT_ADAMAX = (
+    1, 2, 3, 4, 5
+)
+
+
+def optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp=None,
+                   step_buf=None):
+    """One fused optimizer step over the flat fp32 master buffer (+
+    bf16 mirror refresh). ``kind``/``hyper`` are the spec's canonical
+    optimizer name and complete ``optimizer_params``. On GPU the step
+    counter is read from the device ``step_buf`` (capturable)."""
+    if not _on_gpu(p):
+        return ref.optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp)
+    if step_buf is None:
+        raise ValueError("GPU optimizer_step needs a device step_buf")
+    h = hyper
+    lr = float(h["learning_rate"])
+    if kind == "adam" and not h.get("amsgrad"):
+        return _require_hip().adam_step(
+            p, g, s0, s1, lr, float(h["beta_1"]), float(h["beta_2"]),
+            float(h["epsilon"]), int(step), p_lp, step_buf,
+        )
+    flag = False
+    if kind == "sgd":
+        code, vals = _OPT_SGD, [lr, h["momentum"], 0.0, 0.0]
+        flag = bool(h.get("nesterov"))
+    elif kind == "rmsprop":
+        code = _OPT_RMSPROP
+        vals = [lr, h["rho"], h["momentum"], h["epsilon"]]
+    elif kind == "adagrad":
+        code, vals = _OPT_ADAGRAD, [lr, h["epsilon"], 0.0, 0.0]
+    elif kind == "adam":
+        code = _OPT_ADAM_AMSGRAD
+        vals = [lr, h["beta_1"], h["beta_2"], h["epsilon"]]
+    elif kind == "adamax":
+        code = _OPT_ADAMAX
+        vals = [lr, h["beta_1"], h["beta_2"], h["epsilon"]]
+    else:
+        raise ValueError(f"Unsupported optimizer {kind!r}")
+    return _require_hip().optimizer_step(
+        code, p, g, s0, s1, s2, [float(v) for v in vals], flag, p_lp,
+        step_buf,
+    )
+
+
 def lstm_seq_fwd(xW, Wh):
     """Fused on-device LSTM sequence scan (GPU only; H<=64 LDS-resident
     kernels, 64<H<=256 streamed-Wh kernels).

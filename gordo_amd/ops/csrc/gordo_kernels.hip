@@ -902,7 +902,27 @@ torch::Tensor windowed_quantile(torch::Tensor X, int64_t w, double q);
 torch::Tensor row_quantile(torch::Tensor X, double q);
 }  // namespace gordo_thresholds
 
+// configurable loss / optimizer train-step ops (train_ops.hip)
+namespace gordo_train {
+std::vector<torch::Tensor> loss_bwd(torch::Tensor Y, torch::Tensor T,
+                                    int64_t kind, int64_t real_f,
+                                    double delta, bool want_grad);
+void optimizer_step(int64_t kind, torch::Tensor p, torch::Tensor g,
+                    c10::optional<torch::Tensor> s0,
+                    c10::optional<torch::Tensor> s1,
+                    c10::optional<torch::Tensor> s2,
+                    std::vector<double> hyper, bool flag,
+                    c10::optional<torch::Tensor> plp,
+                    torch::Tensor step_buf);
+}  // namespace gordo_train
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("loss_bwd", &gordo_train::loss_bwd,
+          "fused per-model loss (mse/mae/huber/logcosh) + grad + "
+          "accuracy count, one pass over (Y, T)");
+  mod.def("optimizer_step", &gordo_train::optimizer_step,
+          "fused SGD/RMSprop/Adagrad/Adam-amsgrad/Adamax + bf16 mirror "
+          "refresh");
   mod.def("trail_min_max", &gordo_thresholds::trail_min_max,
           "rolling(w).min().max() per row (K10)");
   mod.def("windowed_quantile", &gordo_thresholds::windowed_quantile,

@@ -12,6 +12,7 @@ Layouts (G = models in the pack, B = rows, In/Out = features):
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -117,6 +118,136 @@ def mse_bwd(
     loss = (diff * diff).sum(dim=(1, 2)) / n
     dY = diff * (2.0 / n)
     return loss, dY
+
+
+LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOGCOSH = 0, 1, 2, 3
+
+_LOSS_CODES = {
+    "mse": LOSS_MSE,
+    "mae": LOSS_MAE,
+    "huber": LOSS_HUBER,
+    "logcosh": LOSS_LOGCOSH,
+}
+
+
+def loss_code(name) -> int:
+    """Engine loss code from a CANONICAL loss name (the spec's
+    ``loss_kind``); Keras aliases are resolved in engine/spec.py."""
+    if isinstance(name, int) and name in _LOSS_CODES.values():
+        return name
+    try:
+        return _LOSS_CODES[name]
+    except KeyError:
+        raise ValueError(f"Unsupported loss {name!r}") from None
+
+
+def loss_bwd(
+    Y: torch.Tensor,
+    T: torch.Tensor,
+    loss,
+    real_f: int,
+    delta: float = 1.0,
+    want_grad: bool = True,
+) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """Per-model loss, its gradient and the Keras ``accuracy`` count.
+
+    Y, T: [G, B, Fp]; columns >= ``real_f`` are zero padding. With
+    d = Y - T the per-element losses are mse d², mae |d|, huber
+    (0.5 d² inside ``delta``, linear outside), logcosh log(cosh d); the
+    mean divides by B*real_f and dY = l'(d) / (B*real_f).
+
+    correct[g] counts rows whose argmax over the first ``real_f``
+    columns agrees between Y and T (first maximum wins ties) — Keras
+    categorical accuracy — or, for ``real_f == 1``, rows with
+    t == (y > 0.5) — Keras binary accuracy."""
+    kind = loss_code(loss)
+    d = Y - T
+    a = d.abs()
+    n = Y.shape[1] * int(real_f)
+    if kind == LOSS_MSE:
+        l, gr = d * d, 2.0 * d
+    elif kind == LOSS_MAE:
+        l, gr = a, torch.sign(d)
+    elif kind == LOSS_HUBER:
+        quad = a <= delta
+        l = torch.where(quad, 0.5 * d * d, delta * (a - 0.5 * delta))
+        gr = torch.where(quad, d, delta * torch.sign(d))
+    else:
+        l = a + torch.log1p(torch.exp(-2.0 * a)) - math.log(2.0)
+        l = torch.where(a == 0, torch.zeros_like(l), l)  # exactly 0 at 0
+        gr = torch.tanh(d)
+    loss_out = l.sum(dim=(1, 2)) / n
+    dY = gr / n if want_grad else None
+    y_r, t_r = Y[..., :real_f], T[..., :real_f]
+    if real_f == 1:
+        hit = t_r[..., 0] == (y_r[..., 0] > 0.5).to(t_r.dtype)
+    else:
+        hit = torch.argmax(y_r, dim=-1) == torch.argmax(t_r, dim=-1)
+    correct = hit.sum(dim=1).to(torch.int32)
+    return loss_out, dY, correct
+
+
+def optimizer_step(
+    kind: str,
+    p: torch.Tensor,
+    g: torch.Tensor,
+    s0: Optional[torch.Tensor],
+    s1: Optional[torch.Tensor],
+    s2: Optional[torch.Tensor],
+    hyper: dict,
+    step: int,
+    p_lp: Optional[torch.Tensor] = None,
+):
+    """One in-place optimizer step over a flat fp32 parameter buffer
+    (Keras 3 update rules); refreshes the low-precision mirror when
+    given. ``kind`` is the spec's canonical optimizer name, ``hyper``
+    its complete ``optimizer_params``; s0/s1/s2 are the state slots
+    (m / v / v̂ for Adam; momentum for SGD; v + momentum for RMSprop;
+    the accumulator for Adagrad; m / u for Adamax)."""
+    lr = float(hyper["learning_rate"])
+    if kind == "adam" and not hyper.get("amsgrad"):
+        adam_step(p, g, s0, s1, lr, hyper["beta_1"], hyper["beta_2"],
+                  hyper["epsilon"], step, p_lp)
+        return
+    if kind == "sgd":
+        mu = float(hyper["momentum"])
+        if mu == 0.0:
+            p.add_(g, alpha=-lr)
+        else:
+            s0.mul_(mu).add_(g, alpha=-lr)
+            if hyper.get("nesterov"):
+                p.add_(s0, alpha=mu).add_(g, alpha=-lr)
+            else:
+                p.add_(s0)
+    elif kind == "rmsprop":
+        rho, mu = float(hyper["rho"]), float(hyper["momentum"])
+        s0.mul_(rho).addcmul_(g, g, value=1.0 - rho)
+        inc = lr * g / (s0 + float(hyper["epsilon"])).sqrt_()
+        if mu > 0.0:
+            s1.mul_(mu).add_(inc)
+            p.sub_(s1)
+        else:
+            p.sub_(inc)
+    elif kind == "adagrad":
+        s0.addcmul_(g, g)
+        p.sub_(lr * g / (s0 + float(hyper["epsilon"])).sqrt_())
+    elif kind == "adam":  # amsgrad
+        b1, b2 = float(hyper["beta_1"]), float(hyper["beta_2"])
+        s0.mul_(b1).add_(g, alpha=1.0 - b1)
+        s1.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+        torch.maximum(s2, s1, out=s2)
+        alpha = lr * math.sqrt(1.0 - b2 ** step) / (1.0 - b1 ** step)
+        p.addcdiv_(s0, s2.sqrt().add_(float(hyper["epsilon"])), value=-alpha)
+    elif kind == "adamax":
+        b1, b2 = float(hyper["beta_1"]), float(hyper["beta_2"])
+        s0.mul_(b1).add_(g, alpha=1.0 - b1)
+        torch.maximum(s1 * b2, g.abs(), out=s1)
+        p.addcdiv_(s0, s1 + float(hyper["epsilon"]),
+                   value=-lr / (1.0 - b1 ** step))
+    else:
+        raise ValueError(f"Unsupported optimizer {kind!r}")
+    if p_lp is not None:
+        p_lp.copy_(p)
 
 
 def adam_step(

@@ -38,7 +38,7 @@ from .. import serializer
 from ..builder.build_model import ModelBuilder
 from ..core.base import GordoBaseDataset
 from ..engine.pack import DensePack, LSTMPack
-from ..engine.spec import ModelSpec
+from ..engine.spec import ModelSpec, normalize_loss, normalize_optimizer
 from ..machine import Machine
 from ..machine.metadata import (
     BuildMetadata,
@@ -269,6 +269,32 @@ class PackedFleetBuilder:
             p.error = e
 
     @staticmethod
+    def _canonical_model_def(node):
+        """Model definition with loss / optimizer NAMES normalised, so
+        spelling variants ("adam"/"Adam", "mse"/"mean_squared_error")
+        stay in one prospective group. Names only: `lr` against
+        `learning_rate`, or a default written out, still pre-group
+        apart although `ModelSpec.arch_key` would pack them together.
+        Unknown names pass through; they fail in `_group`."""
+        if isinstance(node, dict):
+            out = {}
+            for k, v in node.items():
+                if isinstance(v, str) and k in ("optimizer", "loss"):
+                    norm = normalize_optimizer if k == "optimizer" \
+                        else normalize_loss
+                    try:
+                        v = norm(v)
+                    except ValueError:
+                        pass
+                else:
+                    v = PackedFleetBuilder._canonical_model_def(v)
+                out[k] = v
+            return out
+        if isinstance(node, (list, tuple)):
+            return [PackedFleetBuilder._canonical_model_def(v) for v in node]
+        return node
+
+    @staticmethod
     def _pre_group(plans: List[MachinePlan]) -> List[List[MachinePlan]]:
         """Config-level grouping done BEFORE any data is fetched, so each
         prospective group's fetch futures can be joined lazily.
@@ -286,7 +312,9 @@ class PackedFleetBuilder:
                     d[k] = len(d[k])
             key = json.dumps(
                 {
-                    "model": p.machine.model,
+                    "model": PackedFleetBuilder._canonical_model_def(
+                        p.machine.model
+                    ),
                     "evaluation": p.machine.evaluation,
                     "dataset": d,
                 },
