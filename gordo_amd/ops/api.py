@@ -309,7 +309,9 @@ def lstm_seq_bwd(dSeq, gacts, cs, Wh, last_only):
 def lstm_seq_bwd_fused(dSeq, gacts, cs, Wh, Wx, last_only):
     """v5 reverse scan with the bwd-data GEMM fused in: returns
     (dG, dX) where dX = dG @ Wx^T computed per step against an
-    LDS-resident WxT (no dG HBM re-read). Geometry: H<=64, F<=128."""
+    LDS-resident WxT (no dG HBM re-read). Geometry: H<=64, F<=128.
+    H%8==0 and F%8==0 take the 16-byte pipelined kernel (bit-identical
+    outputs); ``GORDO_LSTM_PIPE=0`` forces the v5 kernel."""
     if _on_gpu(gacts):
         out = _require_hip().lstm_seq_bwd_fused(
             dSeq, gacts, cs, Wh, Wx, bool(last_only)
@@ -324,8 +326,27 @@ def lstm_seq_bwd_fused(dSeq, gacts, cs, Wh, Wx, last_only):
 
 
 def lstm_seq_bwd_v3(dSeq, gacts, cs, Wh, last_only):
-    """The pipelined backward scan, directly (for A/B tests)."""
+    """The bottom-layer backward scan, directly (for A/B tests): the
+    16-byte pipelined kernel when H % 8 == 0, else the v3 kernel;
+    ``GORDO_LSTM_PIPE=0`` forces v3."""
     return _require_hip().lstm_seq_bwd_v3(dSeq, gacts, cs, Wh, last_only)
+
+
+def lstm_seq_bwd_fused_out(dSeq, gacts, cs, Wh, Wx, last_only, dG, dX):
+    """``lstm_seq_bwd_fused`` (GPU only) writing into caller-provided
+    contiguous, 16-byte-aligned bf16 ``dG`` [G,B,T,4H] and ``dX``
+    [G,B,T,F] — lets tests place the outputs between guard regions."""
+    _require_hip().lstm_seq_bwd_fused_out(
+        dSeq, gacts, cs, Wh, Wx, bool(last_only), dG, dX
+    )
+
+
+def lstm_seq_bwd_v3_out(dSeq, gacts, cs, Wh, last_only, dG):
+    """``lstm_seq_bwd_v3`` (GPU only, H <= 64) into a caller-provided
+    ``dG`` (same contract as ``lstm_seq_bwd_fused_out``)."""
+    _require_hip().lstm_seq_bwd_v3_out(
+        dSeq, gacts, cs, Wh, bool(last_only), dG
+    )
 
 
 def lstm_seq_available(H: int) -> bool:

@@ -893,6 +893,13 @@ std::vector<torch::Tensor> lstm_seq_bwd_fused(
 torch::Tensor lstm_seq_bwd(torch::Tensor dSeq, torch::Tensor gacts,
                            torch::Tensor cs, torch::Tensor Wh,
                            bool last_only);
+void lstm_seq_bwd_fused_out(torch::Tensor dSeq, torch::Tensor gacts,
+                            torch::Tensor cs, torch::Tensor Wh,
+                            torch::Tensor Wx, bool last_only,
+                            torch::Tensor dG, torch::Tensor dX);
+void lstm_seq_bwd_v3_out(torch::Tensor dSeq, torch::Tensor gacts,
+                         torch::Tensor cs, torch::Tensor Wh, bool last_only,
+                         torch::Tensor dG);
 }  // namespace gordo_lstm
 
 // device threshold/statistics kernels (thresholds.hip: K10-K12)
@@ -945,6 +952,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "fused LSTM backward (BPTT) sequence scan");
   mod.def("lstm_seq_bwd_fused", &gordo_lstm::lstm_seq_bwd_fused,
           "v5 reverse scan with dSeq = dG@Wx^T fused in");
+  mod.def("lstm_seq_bwd_fused_out", &gordo_lstm::lstm_seq_bwd_fused_out,
+          "lstm_seq_bwd_fused into caller-provided dG, dX");
+  mod.def("lstm_seq_bwd_v3_out", &gordo_lstm::lstm_seq_bwd_v3_out,
+          "lstm_seq_bwd_v3 into a caller-provided dG");
   mod.def("grouped_linear_fwd", &grouped_linear_fwd,
           "Y = act(X@W + b) per group (MFMA)");
   mod.def("grouped_linear_bwd_data", &grouped_linear_bwd_data,

@@ -375,9 +375,13 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_v5_kernel(
   const int HF = H + F;
 
   // v3-style register prefetch of the next (earlier) step's gate
-  // activations + cell states: their loads depend only on t, so they
-  // issue before the MFMA carry phase and the HBM latency hides under
-  // the matrix work (buffer capped at 8 slots — v3 note).
+  // activations + cell states, meant to issue before the MFMA carry
+  // phase (buffer capped at 8 slots — v3 note). In the generated code
+  // it does NOT overlap: packing two bf16 into one register waits on
+  // the loads inside each slot, and the predicated dSeq load in
+  // gate_bwd costs a vmcnt(0) per slot (docs/kernels.md). This kernel
+  // stays as the bit-exact reference for lstm_seq_bwd_pipe_kernel and
+  // as the path for H % 8 != 0.
   constexpr int MAXE = (ROWS * 64 + 255) / 256;
   constexpr int PF = MAXE > 8 ? 8 : MAXE;
   unsigned int p_if[PF];
@@ -533,6 +537,10 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_v5_kernel(
 // in software. dSeq stays un-prefetched: in the flagship autoencoder
 // path (last_only) it is read only at t=T-1. DORMANT until
 // GPU-validated: dispatched via GORDO_LSTM_V3=1.
+// The overlap described above is not what the compiler emits (see the
+// note at prefetch_step in lstm_seq_bwd_v5_kernel): for H % 8 == 0 the
+// entry point now takes lstm_seq_bwd_pipe_kernel and this kernel is
+// the bit-exact reference and the H % 8 != 0 path.
 // ===========================================================================
 
 template <int ROWS>
@@ -708,6 +716,258 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_v3_kernel(
       }
     }
     __syncthreads();
+  }
+}
+
+// ===========================================================================
+// Pipelined backward scan (H % 8 == 0, H <= 64) — the v5 / v3 math with
+// the per-step memory traffic rebuilt around 16-byte accesses and an
+// LDS ring. Per-element arithmetic and its order are those of
+// lstm_seq_bwd_v5_kernel / lstm_seq_bwd_v3_kernel, so outputs are
+// bit-identical to them.
+//
+//   * the step tile {gacts[rows,t,0:4H], cs[rows,t,0:H], dSeq[rows,t,0:H]}
+//     is fetched as 16-byte chunks into registers, back to back, with
+//     nothing but address arithmetic between issue and use: the row is
+//     clamped to rows_here-1 (dead rows recompute the last live row and
+//     are masked at the stores) and the slot count is compile-time;
+//   * the registers are written to a two-slot LDS ring one iteration
+//     later (after that iteration's MFMA phase), so the tile of step t
+//     is issued in iteration t+3, lands in iteration t+2 and is first
+//     read in iteration t+1 (as c_prev) — its latency has a whole
+//     iteration to hide in. Slot t&1 is dead after the gate phase of
+//     step t, which is when tile t-2 overwrites it;
+//   * c_prev comes from the ring slot of step t-1, not from memory;
+//   * with LAST_ONLY, dh_last seeds dhS once (0 + x is exact), leaving
+//     no dSeq access in the loop;
+//   * dG leaves from dgS and dX from an LDS staging tile as 16-byte
+//     stores. In program order the prefetch loads precede the step's
+//     stores, so the counted wait on the loads leaves the stores in
+//     flight.
+// HAS_DX=false is the bottom-layer scan (no Wx, no dX).
+// ===========================================================================
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+
+template <int ROWS, bool HAS_DX, bool LAST_ONLY>
+__global__ __launch_bounds__(256) void lstm_seq_bwd_pipe_kernel(
+    const bf16* __restrict__ dSeq, const bf16* __restrict__ gacts,
+    const float* __restrict__ cs, const bf16* __restrict__ Wh,
+    const bf16* __restrict__ Wx,   // [G, F, 4H] native (HAS_DX)
+    bf16* __restrict__ dG, bf16* __restrict__ dX,  // dX [G, B, T, F]
+    int B, int T, int H, int F, int ldg) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int H4 = 4 * H;
+  const int Fx = HAS_DX ? F : 0;
+  const int HF = H + Fx;
+  // 16-byte chunks per tile row: 4H bf16 gacts, H f32 cs, H bf16 dSeq
+  const int CPR = (H / 8) * (LAST_ONLY ? 6 : 7);
+  const int RS = CPR * 16;                                 // ring row bytes
+  bf16* WN = reinterpret_cast<bf16*>(smem);                // [H+Fx][ldg]
+  bf16* dgS = WN + (size_t)HF * ldg;                       // [ROWS][ldg]
+  bf16* dhS = dgS + (size_t)ROWS * ldg;                    // [ROWS][LDK]
+  float* dcS = reinterpret_cast<float*>(dhS + (size_t)ROWS * LDK);
+  char* ring = reinterpret_cast<char*>(dcS + (size_t)ROWS * H);
+  bf16* xS = reinterpret_cast<bf16*>(ring + (size_t)2 * ROWS * RS);
+
+  const int nb = (B + ROWS - 1) / ROWS;
+  const int g = blockIdx.x / nb;
+  const int r0 = (blockIdx.x % nb) * ROWS;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int l15 = lane & 15;
+  const int kslot = lane >> 4;
+
+  const bf16* Whg = Wh + (size_t)g * H * H4;
+  const bf16* gag = gacts + ((size_t)g * B + r0) * T * H4;
+  const float* csg = cs + ((size_t)g * B + r0) * T * H;
+  const bf16* dSg = LAST_ONLY ? dSeq + ((size_t)g * B + r0) * H
+                              : dSeq + ((size_t)g * B + r0) * T * H;
+  bf16* dGg = dG + ((size_t)g * B + r0) * T * H4;
+  bf16* dXg = HAS_DX ? dX + ((size_t)g * B + r0) * T * F : nullptr;
+  const int rows_here = min(ROWS, B - r0);
+
+  // ---- per-thread tile slots: source pointer at t = 0 + step stride ----
+  constexpr int MAXS = (ROWS * (LAST_ONLY ? 48 : 56) + 255) / 256;
+  const int total = ROWS * CPR;
+  const char* lsrc[MAXS];
+  int lstr[MAXS];
+  u32x4 R[MAXS];
+  #pragma unroll
+  for (int s = 0; s < MAXS; ++s) {
+    int c = min(tid + s * 256, total - 1);
+    int row = min(c / CPR, rows_here - 1), j = c % CPR;
+    size_t rt = (size_t)row * T;
+    if (j < H / 2) {
+      lsrc[s] = reinterpret_cast<const char*>(gag + rt * H4 + j * 8);
+      lstr[s] = H4 * 2;
+    } else if (LAST_ONLY || j < H / 2 + H / 4) {
+      lsrc[s] = reinterpret_cast<const char*>(csg + rt * H + (j - H / 2) * 4);
+      lstr[s] = H * 4;
+    } else {
+      lsrc[s] = reinterpret_cast<const char*>(
+          dSg + rt * H + (j - H / 2 - H / 4) * 8);
+      lstr[s] = H * 2;
+    }
+  }
+  auto load_tile = [&](int tt) {
+    tt = max(tt, 0);
+    #pragma unroll
+    for (int s = 0; s < MAXS; ++s)
+      R[s] = *reinterpret_cast<const u32x4*>(lsrc[s] + (size_t)tt * lstr[s]);
+  };
+  auto write_tile = [&](int parity) {
+    char* dst = ring + (size_t)parity * ROWS * RS;
+    #pragma unroll
+    for (int s = 0; s < MAXS; ++s) {
+      int c = tid + s * 256;
+      if (c < total) *reinterpret_cast<u32x4*>(dst + c * 16) = R[s];
+    }
+  };
+
+  // ---- per-thread dG / dX store slots (element offsets at t = 0) ----
+  constexpr int DGS = ROWS / 8;    // ROWS * (4H/8) / 256 at H = 64
+  int dg_src[DGS], dg_dst[DGS];
+  #pragma unroll
+  for (int s = 0; s < DGS; ++s) {
+    int q = tid + s * 256;
+    int row = q / (H / 2), j = q % (H / 2);
+    bool ok = row < rows_here;     // rows_here <= ROWS bounds q too
+    dg_src[s] = ok ? row * ldg + j * 8 : -1;
+    dg_dst[s] = ok ? row * T * H4 + j * 8 : 0;
+  }
+  constexpr int DXS = HAS_DX ? ROWS / 16 : 1;  // ROWS * (F/8) / 256 at F = 128
+  int dx_dst[DXS];
+  #pragma unroll
+  for (int s = 0; s < DXS; ++s) {
+    int q = tid + s * 256;
+    int f8 = HAS_DX ? F / 8 : 1;
+    int row = q / f8, j = q % f8;
+    dx_dst[s] = (HAS_DX && row < rows_here) ? row * T * F + j * 8 : -1;
+  }
+
+  // ---- stage weights, zero state, seed dh, fill the ring ----
+  load_tile(T - 1);
+  for (int i = tid; i < H * ldg; i += 256) {
+    int h = i / ldg, n = i % ldg;
+    WN[i] = (n < H4) ? Whg[(size_t)h * H4 + n] : lf2bf(0.f);
+  }
+  if (HAS_DX) {
+    const bf16* Wxg = Wx + (size_t)g * F * H4;
+    bf16* WxN = WN + (size_t)H * ldg;
+    for (int i = tid; i < F * ldg; i += 256) {
+      int f = i / ldg, n = i % ldg;
+      WxN[i] = (n < H4) ? Wxg[(size_t)f * H4 + n] : lf2bf(0.f);
+    }
+  }
+  for (int i = tid; i < ROWS * LDK; i += 256) {
+    int row = i / LDK, col = i % LDK;
+    float v = 0.f;
+    if (LAST_ONLY && col < H && row < rows_here)
+      v = 0.f + lbf2f(dSg[(size_t)row * H + col]);
+    dhS[i] = lf2bf(v);
+  }
+  for (int i = tid; i < ROWS * H; i += 256) dcS[i] = 0.f;
+  for (int i = tid; i < ROWS * ldg; i += 256) dgS[i] = lf2bf(0.f);
+  write_tile((T - 1) & 1);
+  load_tile(T - 2);
+  write_tile(T & 1);
+  load_tile(T - 3);
+  __syncthreads();
+
+  constexpr int FM = ROWS / 16;
+  const int n_items = FM * ((HF + 63) / 64);
+
+  for (int t = T - 1; t >= 0; --t) {
+    // ---- fused gate backward, operands from the ring ----
+    const char* cur = ring + (size_t)(t & 1) * ROWS * RS;
+    const char* prv = ring + (size_t)((t + 1) & 1) * ROWS * RS;
+    for (int e = tid; e < ROWS * H; e += 256) {
+      int row = e / H, hh = e % H;
+      const char* rp = cur + row * RS;
+      const bf16* gp = reinterpret_cast<const bf16*>(rp);
+      float i_g = lbf2f(gp[hh]);
+      float f_g = lbf2f(gp[H + hh]);
+      float g_g = lbf2f(gp[2 * H + hh]);
+      float o_g = lbf2f(gp[3 * H + hh]);
+      float cc = reinterpret_cast<const float*>(rp + 8 * H)[hh];
+      float cp = reinterpret_cast<const float*>(prv + row * RS + 8 * H)[hh];
+      cp = (t > 0) ? cp : 0.f;
+      float dh = lbf2f(dhS[row * LDK + hh]);
+      if (!LAST_ONLY)
+        dh += lbf2f(reinterpret_cast<const bf16*>(rp + 12 * H)[hh]);
+      float tc = fast_tanhf_(cc);
+      float dc = dcS[row * H + hh] + dh * o_g * (1.f - tc * tc);
+      float di = dc * g_g;
+      float df = dc * cp;
+      float dg = dc * i_g;
+      float do_ = dh * tc;
+      dcS[row * H + hh] = dc * f_g;
+      float vi = di * i_g * (1.f - i_g);
+      float vf = df * f_g * (1.f - f_g);
+      float vg = dg * (1.f - g_g * g_g);
+      float vo = do_ * o_g * (1.f - o_g);
+      dgS[row * ldg + hh] = lf2bf(vi);
+      dgS[row * ldg + H + hh] = lf2bf(vf);
+      dgS[row * ldg + 2 * H + hh] = lf2bf(vg);
+      dgS[row * ldg + 3 * H + hh] = lf2bf(vo);
+    }
+    __syncthreads();
+
+    // ---- [dh_carry | dSeq_t] = dgates @ [Wh ; Wx]^T ----
+    for (int item = wid; item < n_items; item += 4) {
+      const int fm = item % FM, col0 = (item / FM) * 64;
+      f32x4 acc[4] = {};
+      for (int kk = 0; kk < H4; kk += 32) {
+        bf16x8 a = *reinterpret_cast<const bf16x8*>(
+            &dgS[(fm * 16 + l15) * ldg + kk + kslot * 8]);
+        #pragma unroll
+        for (int fn = 0; fn < 4; ++fn) {
+          int cc2 = min(col0 + fn * 16 + l15, HF - 1);
+          bf16x8 b = *reinterpret_cast<const bf16x8*>(
+              &WN[(size_t)cc2 * ldg + kk + kslot * 8]);
+          acc[fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a, b, acc[fn], 0, 0, 0);
+        }
+      }
+      #pragma unroll
+      for (int fn = 0; fn < 4; ++fn) {
+        int col = col0 + fn * 16 + l15;
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          int row = fm * 16 + kslot * 4 + r;
+          if (col < H) {
+            dhS[row * LDK + col] = lf2bf(acc[fn][r]);
+          } else if (HAS_DX && col < HF) {
+            xS[row * F + (col - H)] = lf2bf(acc[fn][r]);
+          }
+        }
+      }
+    }
+
+    // ---- land tile t-2, issue tile t-3, then this step's dG ----
+    write_tile(t & 1);
+    load_tile(t - 3);
+    #pragma unroll
+    for (int s = 0; s < DGS; ++s) {
+      if (dg_src[s] >= 0) {
+        *reinterpret_cast<u32x4*>(dGg + (size_t)dg_dst[s] + (size_t)t * H4) =
+            *reinterpret_cast<const u32x4*>(dgS + dg_src[s]);
+      }
+    }
+    __syncthreads();
+
+    // ---- dX of this step from the staging tile (the next MFMA
+    // epilogue rewrites it only after the next barrier) ----
+    if (HAS_DX) {
+      #pragma unroll
+      for (int s = 0; s < DXS; ++s) {
+        if (dx_dst[s] >= 0) {
+          *reinterpret_cast<u32x4*>(dXg + (size_t)dx_dst[s] + (size_t)t * F) =
+              *reinterpret_cast<const u32x4*>(xS + (tid + s * 256) * 8);
+        }
+      }
+    }
   }
 }
 
@@ -1809,9 +2069,60 @@ std::vector<torch::Tensor> lstm_seq_fwd_v3(torch::Tensor xW,
 }
 
 
-std::vector<torch::Tensor> lstm_seq_bwd_fused(
+// ---- pipelined backward scan dispatch ----
+// GORDO_LSTM_PIPE=0 (read per call) restores the v5 / v3 kernels.
+inline bool pipe_enabled() {
+  const char* e = getenv("GORDO_LSTM_PIPE");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
+// F = 0 for the bottom-layer scan (no Wx tile, no dX staging)
+inline size_t pipe_lds(int r, int H, int F, int ldg, bool last_only) {
+  size_t ring_row = (size_t)(H / 8) * (last_only ? 6 : 7) * 16;
+  return (size_t)(H + F) * ldg * 2 + (size_t)r * ldg * 2 +
+         (size_t)r * LDK * 2 + (size_t)r * H * 4 + 2 * (size_t)r * ring_row +
+         (size_t)r * F * 2;
+}
+
+// row tile for the pipelined kernel, 0 when it does not apply: the
+// geometry (16-byte rows), 32-bit per-block store offsets, and the
+// 160 KB LDS budget after halving the tile down to 16 rows
+inline int pipe_rows(int rows, int T, int H, int F, bool has_dx, int ldg,
+                     bool last_only) {
+  if (!pipe_enabled()) return 0;
+  if (H < 8 || H > 64 || H % 8 != 0 || T < 1) return 0;
+  if (has_dx && (F < 8 || F > 128 || F % 8 != 0)) return 0;
+  if ((size_t)64 * T * 256 >= ((size_t)1 << 31)) return 0;
+  while (rows > 16 && pipe_lds(rows, H, F, ldg, last_only) > 160 * 1024)
+    rows /= 2;
+  return pipe_lds(rows, H, F, ldg, last_only) <= 160 * 1024 ? rows : 0;
+}
+
+#define GORDO_PIPE_LAUNCH(R, DX, LO)                                       \
+  hipLaunchKernelGGL((lstm_seq_bwd_pipe_kernel<R, DX, LO>), dim3(blocks),  \
+                     dim3(256), lds, stream, dp, gp, cp, whp, wxp, dgp,    \
+                     dxp, B, T, H, F, ldg)
+#define GORDO_PIPE_ROWS(DX, LO)                                            \
+  do {                                                                     \
+    if (rows == 64) GORDO_PIPE_LAUNCH(64, DX, LO);                         \
+    else if (rows == 32) GORDO_PIPE_LAUNCH(32, DX, LO);                    \
+    else GORDO_PIPE_LAUNCH(16, DX, LO);                                    \
+  } while (0)
+
+inline void check_out(const torch::Tensor& out, const torch::Tensor& like,
+                      std::vector<int64_t> shape, const char* what) {
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kBFloat16 &&
+                  out.is_contiguous() && out.sizes().vec() == shape &&
+                  out.device() == like.device() &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              what, " must be a contiguous 16-byte-aligned bf16 tensor of "
+              "the output shape on the inputs' device");
+}
+
+std::vector<torch::Tensor> lstm_seq_bwd_fused_impl(
     torch::Tensor dSeq, torch::Tensor gacts, torch::Tensor cs,
-    torch::Tensor Wh, torch::Tensor Wx, bool last_only) {
+    torch::Tensor Wh, torch::Tensor Wx, bool last_only,
+    c10::optional<torch::Tensor> dG_out, c10::optional<torch::Tensor> dX_out) {
   // returns {dG, dX}: the reverse scan with dSeq_t = dG_t @ Wx^T
   // fused in (see kernel note). Geometry: H <= 64, F <= 128.
   TORCH_CHECK(gacts.is_cuda() && gacts.dim() == 4, "gacts must be [G,B,T,4H]");
@@ -1824,17 +2135,11 @@ std::vector<torch::Tensor> lstm_seq_bwd_fused(
   int H = H4 / 4, F = Wxc.size(1);
   TORCH_CHECK(H <= 64 && F <= 128, "lstm_seq_bwd_fused geometry");
   int ldg = pad_ldg(H4);
-  auto dG = torch::empty_like(gc);
-  auto dX = torch::empty({G, B, T, F}, gc.options());
+  if (dG_out) check_out(*dG_out, gc, {G, B, T, H4}, "dG");
+  if (dX_out) check_out(*dX_out, gc, {G, B, T, F}, "dX");
+  auto dG = dG_out ? *dG_out : torch::empty_like(gc);
+  auto dX = dX_out ? *dX_out : torch::empty({G, B, T, F}, gc.options());
   int rows = pick_rows(G, B);
-  auto lds_for = [&](int r) {
-    return (size_t)H * ldg * 2 + (size_t)F * ldg * 2 +
-           (size_t)r * ldg * 2 + (size_t)r * LDK * 2 + (size_t)r * H * 4;
-  };
-  while (rows > 16 && lds_for(rows) > 160 * 1024) rows /= 2;
-  size_t lds = lds_for(rows);
-  TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded (v5 bwd)");
-  int blocks = G * ((B + rows - 1) / rows);
   auto stream = at::cuda::getCurrentCUDAStream().stream();
   auto dp = (const bf16*)dc.data_ptr();
   auto gp = (const bf16*)gc.data_ptr();
@@ -1843,6 +2148,22 @@ std::vector<torch::Tensor> lstm_seq_bwd_fused(
   auto wxp = (const bf16*)Wxc.data_ptr();
   auto dgp = (bf16*)dG.data_ptr();
   auto dxp = (bf16*)dX.data_ptr();
+  if (int prow = pipe_rows(rows, T, H, F, true, ldg, last_only)) {
+    rows = prow;
+    size_t lds = pipe_lds(rows, H, F, ldg, last_only);
+    int blocks = G * ((B + rows - 1) / rows);
+    if (last_only) GORDO_PIPE_ROWS(true, true);
+    else GORDO_PIPE_ROWS(true, false);
+    return {dG, dX};
+  }
+  auto lds_for = [&](int r) {
+    return (size_t)H * ldg * 2 + (size_t)F * ldg * 2 +
+           (size_t)r * ldg * 2 + (size_t)r * LDK * 2 + (size_t)r * H * 4;
+  };
+  while (rows > 16 && lds_for(rows) > 160 * 1024) rows /= 2;
+  size_t lds = lds_for(rows);
+  TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded (v5 bwd)");
+  int blocks = G * ((B + rows - 1) / rows);
   int lo = last_only ? 1 : 0;
   if (rows == 64)
     hipLaunchKernelGGL(lstm_seq_bwd_v5_kernel<64>, dim3(blocks), dim3(256),
@@ -1859,15 +2180,34 @@ std::vector<torch::Tensor> lstm_seq_bwd_fused(
   return {dG, dX};
 }
 
-torch::Tensor lstm_seq_bwd_v3(torch::Tensor dSeq, torch::Tensor gacts,
-                              torch::Tensor cs, torch::Tensor Wh,
-                              bool last_only) {
+std::vector<torch::Tensor> lstm_seq_bwd_fused(
+    torch::Tensor dSeq, torch::Tensor gacts, torch::Tensor cs,
+    torch::Tensor Wh, torch::Tensor Wx, bool last_only) {
+  return lstm_seq_bwd_fused_impl(dSeq, gacts, cs, Wh, Wx, last_only,
+                                 c10::nullopt, c10::nullopt);
+}
+
+// the same scan writing into caller-provided dG / dX (tests place them
+// inside guard regions)
+void lstm_seq_bwd_fused_out(torch::Tensor dSeq, torch::Tensor gacts,
+                            torch::Tensor cs, torch::Tensor Wh,
+                            torch::Tensor Wx, bool last_only,
+                            torch::Tensor dG, torch::Tensor dX) {
+  lstm_seq_bwd_fused_impl(dSeq, gacts, cs, Wh, Wx, last_only, dG, dX);
+}
+
+torch::Tensor lstm_seq_bwd_v3_impl(torch::Tensor dSeq, torch::Tensor gacts,
+                                   torch::Tensor cs, torch::Tensor Wh,
+                                   bool last_only,
+                                   c10::optional<torch::Tensor> dG_out) {
   // identical contract to lstm_seq_bwd; pipelined kernel, always the
   // barriered layout (A/B-tested against v1 on the same shapes).
   // H > 64 routes to the big-H kernel (no v3 there).
   TORCH_CHECK(gacts.is_cuda() && gacts.dim() == 4, "gacts must be [G,B,T,4H]");
-  if (gacts.size(3) / 4 > 64)
+  if (gacts.size(3) / 4 > 64) {
+    TORCH_CHECK(!dG_out, "no out variant on the big-H path");
     return lstm_seq_bwd_big(dSeq, gacts, cs, Wh, last_only);
+  }
   auto dc = dSeq.to(torch::kBFloat16).contiguous();
   auto gc = gacts.to(torch::kBFloat16).contiguous();
   auto cc = cs.to(torch::kFloat32).contiguous();
@@ -1876,8 +2216,26 @@ torch::Tensor lstm_seq_bwd_v3(torch::Tensor dSeq, torch::Tensor gacts,
   int H = H4 / 4;
   TORCH_CHECK(H <= 64, "lstm_seq_bwd_v3 supports H <= 64");
   int ldg = pad_ldg(H4);
-  auto dG = torch::empty_like(gc);
+  if (dG_out) check_out(*dG_out, gc, {G, B, T, H4}, "dG");
+  auto dG = dG_out ? *dG_out : torch::empty_like(gc);
   int rows = pick_rows(G, B);
+  if (int prow = pipe_rows(rows, T, H, 0, false, ldg, last_only)) {
+    rows = prow;
+    const int F = 0;
+    size_t lds = pipe_lds(rows, H, F, ldg, last_only);
+    int blocks = G * ((B + rows - 1) / rows);
+    auto stream = at::cuda::getCurrentCUDAStream().stream();
+    auto dp = (const bf16*)dc.data_ptr();
+    auto gp = (const bf16*)gc.data_ptr();
+    auto cp = cc.data_ptr<float>();
+    auto whp = (const bf16*)Whc.data_ptr();
+    const bf16* wxp = nullptr;
+    auto dgp = (bf16*)dG.data_ptr();
+    bf16* dxp = nullptr;
+    if (last_only) GORDO_PIPE_ROWS(false, true);
+    else GORDO_PIPE_ROWS(false, false);
+    return dG;
+  }
   size_t lds = (size_t)H * ldg * 2 + (size_t)rows * ldg * 2 +
                (size_t)rows * LDK * 2 + (size_t)rows * H * 4;
   TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded");
@@ -1902,6 +2260,18 @@ torch::Tensor lstm_seq_bwd_v3(torch::Tensor dSeq, torch::Tensor gacts,
                        (const bf16*)Whc.data_ptr(), (bf16*)dG.data_ptr(), B,
                        T, H, ldg, last_only ? 1 : 0);
   return dG;
+}
+
+torch::Tensor lstm_seq_bwd_v3(torch::Tensor dSeq, torch::Tensor gacts,
+                              torch::Tensor cs, torch::Tensor Wh,
+                              bool last_only) {
+  return lstm_seq_bwd_v3_impl(dSeq, gacts, cs, Wh, last_only, c10::nullopt);
+}
+
+void lstm_seq_bwd_v3_out(torch::Tensor dSeq, torch::Tensor gacts,
+                         torch::Tensor cs, torch::Tensor Wh, bool last_only,
+                         torch::Tensor dG) {
+  lstm_seq_bwd_v3_impl(dSeq, gacts, cs, Wh, last_only, dG);
 }
 
 torch::Tensor lstm_seq_bwd(torch::Tensor dSeq, torch::Tensor gacts,
@@ -1970,5 +2340,8 @@ torch::Tensor lstm_seq_bwd(torch::Tensor dSeq, torch::Tensor gacts,
                        T, H, ldg, last_only ? 1 : 0);
   return dG;
 }
+
+#undef GORDO_PIPE_ROWS
+#undef GORDO_PIPE_LAUNCH
 
 }  // namespace gordo_lstm
