@@ -286,6 +286,41 @@ def lstm_seq_fwd_v3(xW, Wh):
     return _require_hip().lstm_seq_fwd_v3(xW, Wh)
 
 
+def lstm_seq_fwd_v2(xW, Wh):
+    """The barrier-free v2 forward scan, directly (H % 16 == 0,
+    H <= 64): the extension entry takes v2 at any grid size, without
+    the fill gate of ``lstm_seq_fwd``."""
+    H = xW.shape[-1] // 4
+    if H % 16 != 0 or H > 64:
+        raise ValueError("lstm_seq_fwd_v2 needs H % 16 == 0 and H <= 64")
+    return _require_hip().lstm_seq_fwd(xW, Wh)
+
+
+def lstm_seq_bwd_v2(dSeq, gacts, cs, Wh, last_only):
+    """The barrier-free v2 backward scan, directly (same geometry and
+    purpose as ``lstm_seq_fwd_v2``)."""
+    H = gacts.shape[-1] // 4
+    if H % 16 != 0 or H > 64:
+        raise ValueError("lstm_seq_bwd_v2 needs H % 16 == 0 and H <= 64")
+    return _require_hip().lstm_seq_bwd(dSeq, gacts, cs, Wh, bool(last_only))
+
+
+def last_scan_launch() -> dict:
+    """Which scan kernel this thread's last ``lstm_seq_*`` call
+    launched: ``family`` (fwd_v1/v2/v3/v4/big, bwd_v1/v2/v3/v5/pipe/
+    big), ``rows`` (row tile; 64 for v2), ``hf`` (H/16, v2 only, else
+    None) and, for bwd_pipe only, ``has_dx`` / ``last_only`` (else
+    None). Host-side record; ``family`` is "" before any launch."""
+    family, rows, hf, has_dx, last_only = _require_hip().last_scan_launch()
+    return {
+        "family": family,
+        "rows": rows,
+        "hf": hf if hf > 0 else None,
+        "has_dx": None if has_dx < 0 else bool(has_dx),
+        "last_only": None if last_only < 0 else bool(last_only),
+    }
+
+
 def lstm_seq_bwd(dSeq, gacts, cs, Wh, last_only):
     """Fused on-device LSTM backward (BPTT) scan (GPU only). Same
     version dispatch as ``lstm_seq_fwd``: pipelined v3 by default for

@@ -900,6 +900,7 @@ void lstm_seq_bwd_fused_out(torch::Tensor dSeq, torch::Tensor gacts,
 void lstm_seq_bwd_v3_out(torch::Tensor dSeq, torch::Tensor gacts,
                          torch::Tensor cs, torch::Tensor Wh, bool last_only,
                          torch::Tensor dG);
+std::tuple<std::string, int, int, int, int> last_scan_launch();
 }  // namespace gordo_lstm
 
 // device threshold/statistics kernels (thresholds.hip: K10-K12)
@@ -954,6 +955,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "v5 reverse scan with dSeq = dG@Wx^T fused in");
   mod.def("lstm_seq_bwd_fused_out", &gordo_lstm::lstm_seq_bwd_fused_out,
           "lstm_seq_bwd_fused into caller-provided dG, dX");
+  mod.def("last_scan_launch", &gordo_lstm::last_scan_launch,
+          "(family, rows, hf, has_dx, last_only) of this thread's last "
+          "scan-kernel launch");
   mod.def("lstm_seq_bwd_v3_out", &gordo_lstm::lstm_seq_bwd_v3_out,
           "lstm_seq_bwd_v3 into a caller-provided dG");
   mod.def("grouped_linear_fwd", &grouped_linear_fwd,

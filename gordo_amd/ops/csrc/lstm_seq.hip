@@ -25,6 +25,8 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include <string>
+#include <tuple>
 #include <vector>
 
 #define DEV_INLINE __device__ __forceinline__
@@ -1785,6 +1787,29 @@ __global__ __launch_bounds__(256) void lstm_seq_fwd_v4_kernel(
 // ---------------------------------------------------------------------------
 namespace gordo_lstm {
 
+// Launch record: which scan kernel the calling thread launched last
+// (host-only; tests assert the dispatch arm they mean to exercise).
+// rows is the row tile (64 for v2, whose HF = H/16 goes in hf);
+// has_dx / last_only are -1 outside the pipelined backward.
+struct ScanLaunch {
+  const char* family = "";
+  int rows = 0;
+  int hf = 0;
+  int has_dx = -1;
+  int last_only = -1;
+};
+thread_local ScanLaunch g_last_launch;
+
+inline void note_launch(const char* family, int rows, int hf = 0,
+                        int has_dx = -1, int last_only = -1) {
+  g_last_launch = ScanLaunch{family, rows, hf, has_dx, last_only};
+}
+
+std::tuple<std::string, int, int, int, int> last_scan_launch() {
+  const ScanLaunch& l = g_last_launch;
+  return {std::string(l.family), l.rows, l.hf, l.has_dx, l.last_only};
+}
+
 // pad 4H up to the MFMA K-step (32) plus 8: the K loop's last
 // fragment read may touch columns [H4, ru32(H4)); they must exist in
 // the row and be zero.
@@ -1846,6 +1871,7 @@ std::vector<torch::Tensor> lstm_seq_fwd_big(torch::Tensor xW,
   TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded (big fwd)");
   int blocks = G * ((B + rows - 1) / rows);
   auto stream = at::cuda::getCurrentCUDAStream().stream();
+  note_launch("fwd_big", rows);
   if (rows == 64)
     hipLaunchKernelGGL(lstm_seq_fwd_big_kernel<64>, dim3(blocks), dim3(256),
                        lds, stream, (const bf16*)xc.data_ptr(),
@@ -1880,6 +1906,7 @@ torch::Tensor lstm_seq_bwd_big(torch::Tensor dSeq, torch::Tensor gacts,
   TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded (big bwd)");
   int blocks = G * ((B + rows - 1) / rows);
   auto stream = at::cuda::getCurrentCUDAStream().stream();
+  note_launch("bwd_big", rows);
   if (rows == 64)
     hipLaunchKernelGGL(lstm_seq_bwd_big_kernel<64>, dim3(blocks), dim3(256),
                        lds, stream, (const bf16*)dc.data_ptr(),
@@ -1947,6 +1974,7 @@ std::vector<torch::Tensor> lstm_seq_fwd_fused(torch::Tensor xseq,
     hipLaunchKernelGGL((lstm_seq_fwd_v4_kernel<R, S>), dim3(blocks),   \
                        dim3(256), lds, stream, xp, wp, bp, hp, cp, gp, \
                        B, T, H, F, ldg)
+  note_launch("fwd_v4", rows);
   if (store_aux) {
     if (rows == 64) V4_LAUNCH(64, true);
     else if (rows == 32) V4_LAUNCH(32, true);
@@ -1988,6 +2016,7 @@ std::vector<torch::Tensor> lstm_seq_fwd(torch::Tensor xW, torch::Tensor Wh) {
     auto hp = (bf16*)hs.data_ptr();
     auto cp = cs.data_ptr<float>();
     auto gp = (bf16*)gacts.data_ptr();
+    note_launch("fwd_v2", 64, H / 16);
     switch (H / 16) {
       case 1: hipLaunchKernelGGL(lstm_seq_fwd_v2_kernel<1>, dim3(blocks2),
                                  dim3(256), lds2, stream, xp, wp, hp, cp, gp,
@@ -2004,6 +2033,7 @@ std::vector<torch::Tensor> lstm_seq_fwd(torch::Tensor xW, torch::Tensor Wh) {
     }
     return {hs, cs, gacts};
   }
+  note_launch("fwd_v1", rows);
   if (rows == 64)
     hipLaunchKernelGGL(lstm_seq_fwd_kernel<64>, dim3(blocks), dim3(256), lds,
                        stream, (const bf16*)xc.data_ptr(),
@@ -2047,6 +2077,7 @@ std::vector<torch::Tensor> lstm_seq_fwd_v3(torch::Tensor xW,
   TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded");
   int blocks = G * ((B + rows - 1) / rows);
   auto stream = at::cuda::getCurrentCUDAStream().stream();
+  note_launch("fwd_v3", rows);
   if (rows == 64)
     hipLaunchKernelGGL(lstm_seq_fwd_v3_kernel<64>, dim3(blocks), dim3(256),
                        lds, stream, (const bf16*)xc.data_ptr(),
@@ -2152,6 +2183,7 @@ std::vector<torch::Tensor> lstm_seq_bwd_fused_impl(
     rows = prow;
     size_t lds = pipe_lds(rows, H, F, ldg, last_only);
     int blocks = G * ((B + rows - 1) / rows);
+    note_launch("bwd_pipe", rows, 0, 1, last_only ? 1 : 0);
     if (last_only) GORDO_PIPE_ROWS(true, true);
     else GORDO_PIPE_ROWS(true, false);
     return {dG, dX};
@@ -2165,6 +2197,7 @@ std::vector<torch::Tensor> lstm_seq_bwd_fused_impl(
   TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded (v5 bwd)");
   int blocks = G * ((B + rows - 1) / rows);
   int lo = last_only ? 1 : 0;
+  note_launch("bwd_v5", rows);
   if (rows == 64)
     hipLaunchKernelGGL(lstm_seq_bwd_v5_kernel<64>, dim3(blocks), dim3(256),
                        lds, stream, dp, gp, cp, whp, wxp, dgp, dxp, B, T,
@@ -2232,6 +2265,7 @@ torch::Tensor lstm_seq_bwd_v3_impl(torch::Tensor dSeq, torch::Tensor gacts,
     const bf16* wxp = nullptr;
     auto dgp = (bf16*)dG.data_ptr();
     bf16* dxp = nullptr;
+    note_launch("bwd_pipe", rows, 0, 0, last_only ? 1 : 0);
     if (last_only) GORDO_PIPE_ROWS(false, true);
     else GORDO_PIPE_ROWS(false, false);
     return dG;
@@ -2241,6 +2275,7 @@ torch::Tensor lstm_seq_bwd_v3_impl(torch::Tensor dSeq, torch::Tensor gacts,
   TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded");
   int blocks = G * ((B + rows - 1) / rows);
   auto stream = at::cuda::getCurrentCUDAStream().stream();
+  note_launch("bwd_v3", rows);
   if (rows == 64)
     hipLaunchKernelGGL(lstm_seq_bwd_v3_kernel<64>, dim3(blocks), dim3(256),
                        lds, stream, (const bf16*)dc.data_ptr(),
@@ -2304,6 +2339,7 @@ torch::Tensor lstm_seq_bwd(torch::Tensor dSeq, torch::Tensor gacts,
     auto wp = (const bf16*)Whc.data_ptr();
     auto op = (bf16*)dG.data_ptr();
     int lo = last_only ? 1 : 0;
+    note_launch("bwd_v2", 64, H / 16);
     switch (H / 16) {
       case 1: hipLaunchKernelGGL(lstm_seq_bwd_v2_kernel<1>, dim3(blocks2),
                                  dim3(256), lds2, stream, dp, gp, cp, wp, op,
@@ -2320,6 +2356,7 @@ torch::Tensor lstm_seq_bwd(torch::Tensor dSeq, torch::Tensor gacts,
     }
     return dG;
   }
+  note_launch("bwd_v1", rows);
   if (rows == 64)
     hipLaunchKernelGGL(lstm_seq_bwd_kernel<64>, dim3(blocks), dim3(256), lds,
                        stream, (const bf16*)dc.data_ptr(),

@@ -337,3 +337,106 @@ def lstm_pointwise_bwd(
         dim=-1,
     )
     return dgates, dc_prev
+
+
+# ---------------------------------------------------------------------------
+# High-precision oracle of the fused LSTM sequence scans. Plain torch,
+# independent of every other op here. With ``round_points=True`` values
+# pass through bf16 exactly where the scan kernels store or feed back
+# bf16: h (before it re-enters the recurrence, and in ``hs``), the
+# activated gates ``gacts``, dG (before the dG @ Wh^T carry, and in the
+# output) and dX. c, dc and the dh carry stay unrounded. Inputs are
+# used as passed: callers wanting the kernel's view pass bf16-rounded
+# tensors. With ``round_points=False`` the functions are the exact
+# (differentiable) recurrence and its analytic gradient.
+# ---------------------------------------------------------------------------
+
+
+def _bf16_round(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+def _scan_fwd(gate_x, B, T, Wh, b, dtype, round_points):
+    """gate_x(t) -> x-side pre-activation [G,B,4H] of step t."""
+    rnd = _bf16_round if round_points else (lambda t: t)
+    Wh = Wh.to(dtype)
+    G, H = Wh.shape[0], Wh.shape[1]
+    h = torch.zeros(G, B, H, dtype=dtype)
+    c = torch.zeros(G, B, H, dtype=dtype)
+    hs, cs, gas = [], [], []
+    for t in range(T):
+        gates = gate_x(t) + torch.bmm(h, Wh)
+        if b is not None:
+            gates = gates + b.to(dtype).unsqueeze(1)
+        i = torch.sigmoid(gates[..., 0 * H:1 * H])
+        f = torch.sigmoid(gates[..., 1 * H:2 * H])
+        g = torch.tanh(gates[..., 2 * H:3 * H])
+        o = torch.sigmoid(gates[..., 3 * H:4 * H])
+        c = f * c + i * g
+        h = rnd(o * torch.tanh(c))
+        hs.append(h)
+        cs.append(c)
+        gas.append(rnd(torch.cat([i, f, g, o], dim=-1)))
+    return torch.stack(hs, 2), torch.stack(cs, 2), torch.stack(gas, 2)
+
+
+def lstm_seq_fwd_ref(xW, Wh, *, dtype=torch.float64, round_points=True):
+    """Forward scan over precomputed x-side gates xW [G,B,T,4H] with
+    Wh [G,H,4H] (gate order i, f, g, o; h_0 = c_0 = 0). Returns
+    ``(hs [G,B,T,H], cs [G,B,T,H], gacts [G,B,T,4H])`` in ``dtype``."""
+    xW = xW.to(dtype)
+    return _scan_fwd(lambda t: xW[:, :, t], xW.shape[1], xW.shape[2], Wh,
+                     None, dtype, round_points)
+
+
+def lstm_seq_fwd_fused_ref(x, Wx, Wh, b, *, dtype=torch.float64,
+                           round_points=True):
+    """Same scan with the x-side product x_t @ Wx + b formed inside the
+    step and added unrounded (x [G,B,T,F], Wx [G,F,4H], b [G,4H])."""
+    x, Wx = x.to(dtype), Wx.to(dtype)
+    return _scan_fwd(lambda t: torch.bmm(x[:, :, t], Wx), x.shape[1],
+                     x.shape[2], Wh, b, dtype, round_points)
+
+
+def lstm_seq_bwd_ref(dSeq, gacts, cs, Wh, last_only, *, Wx=None,
+                     dtype=torch.float64, round_points=True):
+    """Reverse (BPTT) scan: pre-activation gate grads dG [G,B,T,4H]
+    from upstream grads on the h sequence (dSeq [G,B,T,H], or [G,B,H]
+    on h_{T-1} alone when ``last_only``) and the forward's ``gacts`` /
+    ``cs``. With ``Wx`` [G,F,4H] also returns dX = dG @ Wx^T."""
+    rnd = _bf16_round if round_points else (lambda t: t)
+    dSeq, gacts, cs, Wh = (t.to(dtype) for t in (dSeq, gacts, cs, Wh))
+    G, B, T, H4 = gacts.shape
+    H = H4 // 4
+    WhT = Wh.transpose(1, 2)
+    WxT = Wx.to(dtype).transpose(1, 2) if Wx is not None else None
+    dh_carry = torch.zeros(G, B, H, dtype=dtype)
+    dc = torch.zeros(G, B, H, dtype=dtype)
+    dG = [None] * T
+    dX = [None] * T
+    for t in range(T - 1, -1, -1):
+        dh = dh_carry
+        if not last_only:
+            dh = dh + dSeq[:, :, t]
+        elif t == T - 1:
+            dh = dh + dSeq
+        ga = gacts[:, :, t]
+        i, f = ga[..., 0 * H:1 * H], ga[..., 1 * H:2 * H]
+        g, o = ga[..., 2 * H:3 * H], ga[..., 3 * H:4 * H]
+        c_prev = cs[:, :, t - 1] if t > 0 else torch.zeros_like(dc)
+        tc = torch.tanh(cs[:, :, t])
+        dc = dc + dh * o * (1.0 - tc * tc)
+        dg_t = rnd(torch.cat([
+            dc * g * i * (1.0 - i),
+            dc * c_prev * f * (1.0 - f),
+            dc * i * (1.0 - g * g),
+            dh * tc * o * (1.0 - o),
+        ], dim=-1))
+        dc = dc * f
+        dG[t] = dg_t
+        dh_carry = torch.bmm(dg_t, WhT)
+        if WxT is not None:
+            dX[t] = rnd(torch.bmm(dg_t, WxT))
+    if WxT is None:
+        return torch.stack(dG, 2)
+    return torch.stack(dG, 2), torch.stack(dX, 2)

@@ -88,11 +88,13 @@ def test_grouped_linear_bwd_data(G, M, N, K):
 
 @pytest.mark.parametrize(
     "G,M,K,N", [
-        (2, 200, 50, 38),      # legacy scalar staging (K,N not 8-mult)
-        (1, 4176, 40, 160),    # vectorized A+Z staging (pad8 layout)
-        (4, 37, 19, 21),       # ragged tails, scalar path
-        (2, 333, 56, 48),      # vectorized with ragged M tail
-        (1, 512, 48, 21),      # vecA + legacy Z mix
+        # A and Z staging is element-wise at every alignment (the
+        # 16-byte staging variants are compiled out)
+        (2, 200, 50, 38),      # K, N not multiples of 8
+        (1, 4176, 40, 160),    # pad8 layout, big M
+        (4, 37, 19, 21),       # ragged tails
+        (2, 333, 56, 48),      # 8-aligned K, N with ragged M tail
+        (1, 512, 48, 21),      # 8-aligned K, odd N
     ]
 )
 def test_grouped_linear_wgrad(G, M, K, N):
@@ -104,6 +106,83 @@ def test_grouped_linear_wgrad(G, M, K, N):
     tol = dict(rtol=3e-2, atol=2e-2 * max(1.0, (M / 256) ** 0.5))
     torch.testing.assert_close(gotW.cpu(), wantW, **tol)
     torch.testing.assert_close(gotb.cpu(), wantb, **tol)
+
+
+def _wgrad_oracle(A, dZ):
+    """fp64 bmm on the bf16-rounded inputs, and the bound the kernel's
+    fp32 result must keep against it: 4x the error of the same product
+    in fp32 on the CPU, floored at 2 ulps of the fp32 output."""
+    A, dZ = (t.to(torch.bfloat16).double() for t in (A, dZ))
+    want_W = torch.bmm(A.transpose(1, 2), dZ)
+    want_b = dZ.sum(dim=1)
+    emu_W = torch.bmm(A.float().transpose(1, 2), dZ.float())
+    emu_b = dZ.float().sum(dim=1)
+    atol_W = 4 * (emu_W.double() - want_W).abs().max().item()
+    atol_b = 4 * (emu_b.double() - want_b).abs().max().item()
+    return (want_W, atol_W), (want_b, atol_b)
+
+
+def _check_wgrad(name, got, want_atol):
+    want, atol = want_atol
+    assert got.dtype == torch.float32
+    err = (got.double().cpu() - want).abs()
+    bound = torch.clamp(2.0 ** -22 * want.abs(), min=atol)
+    print(f"{name}: max abs err {err.max().item():.3e}, atol {atol:.3e}, "
+          f"scale {want.abs().max().item():.3e}")
+    assert bool((err <= bound).all()), (
+        f"{name}: max err {err.max().item():.3e} beyond "
+        f"max({atol:.3e}, 2^-22 |want|)"
+    )
+
+
+@pytest.mark.parametrize(
+    "G,M,K,N", [
+        # single M-chunk (gridDim.y == 1): dW is plain-stored into an
+        # uninitialised buffer
+        (2, 20, 50, 38),
+        (1, 32, 8, 8),
+        (1100, 40, 8, 8),      # many blocks: the split-M target is 1
+        # split-M with more than one K tile (and N tile): db must come
+        # from the k0 == 0 blocks only
+        (2, 200, 72, 38),
+        (1, 100, 130, 70),
+    ]
+)
+def test_grouped_linear_wgrad_arms_vs_fp64(G, M, K, N):
+    require_hip()
+    X, dZ = _rand(G, M, K, seed=6), _rand(G, M, N, seed=7) * 0.1
+    want_W, want_b = _wgrad_oracle(X, dZ)
+    gotW, gotb = ops.grouped_linear_wgrad(to_dev_bf16(X), to_dev_bf16(dZ))
+    _check_wgrad("dW", gotW, want_W)
+    _check_wgrad("db", gotb, want_b)
+
+
+@pytest.mark.parametrize("G,B,T,F,H", [
+    (2, 4, 5, 34, 16),      # single M-chunk (M = 20), K = 50
+    (1, 10, 10, 66, 64),    # split-M, K = 130 (3 tiles), N = 256 (4 tiles)
+])
+def test_grouped_wgrad_xh_arms_vs_fp64(G, B, T, F, H):
+    """The combined {dWx, dWh, db} pass against the fp64 oracle, in the
+    same two arms, and against the separate calls."""
+    require_hip()
+    seq = _rand(G, B * T, F, seed=64)
+    hs = _rand(G, B, T, H, seed=65)
+    dG = _rand(G, B * T, 4 * H, seed=66) * 0.1
+    h_prev = torch.cat(
+        [torch.zeros_like(hs[:, :, :1]), hs[:, :, :-1]], dim=2
+    ).reshape(G, B * T, H)
+    want_Wx, want_b = _wgrad_oracle(seq, dG)
+    want_Wh, _ = _wgrad_oracle(h_prev, dG)
+    d_seq, d_hs, d_dG = to_dev_bf16(seq), to_dev_bf16(hs), to_dev_bf16(dG)
+    got_Wx, got_Wh, got_b = ops.grouped_wgrad_xh(d_seq, d_hs, d_dG, T)
+    _check_wgrad("dWx", got_Wx.contiguous(), want_Wx)
+    _check_wgrad("dWh", got_Wh.contiguous(), want_Wh)
+    _check_wgrad("db", got_b, want_b)
+    sep_Wx, sep_b = ops.grouped_linear_wgrad(d_seq, d_dG)
+    sep_Wh, _ = ops.grouped_linear_wgrad_hprev(d_hs, d_dG, T)
+    torch.testing.assert_close(got_Wx, sep_Wx, rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(got_Wh, sep_Wh, rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(got_b, sep_b, rtol=1e-5, atol=1e-5)
 
 
 def test_grouped_gemm_acc():
@@ -301,6 +380,52 @@ def test_anomaly_score_kernel_vs_pandas():
                                rtol=1e-5, atol=1e-6)
 
 
+@pytest.mark.parametrize("with_thr", [True, False])
+def test_anomaly_score_kernel_wide_ragged(with_thr):
+    """F = 130 (three trips of the 64-lane column loop, the last one
+    partial), N = 5 (a ragged last block of 4 rows), with and without
+    feature thresholds; numpy formulas at the tolerances above."""
+    require_hip()
+    from sklearn.preprocessing import MinMaxScaler
+
+    rng = np.random.default_rng(7)
+    N, F = 5, 130
+    out = rng.random((N, F)).astype("float32")
+    y = rng.random((N, F)).astype("float32")
+    scaler = MinMaxScaler().fit(rng.random((200, F)) * 3)
+    thr = rng.random(F).astype("float32") + 0.1
+    agg = 0.37
+
+    ts_ref = np.abs(scaler.transform(out) - scaler.transform(y))
+    tots_ref = (ts_ref ** 2).mean(axis=1)
+    tu_ref = np.abs(out - y)
+    totu_ref = (tu_ref ** 2).mean(axis=1)
+
+    ts, tots, tu, totu, conf, tconf = ops.anomaly_score(
+        torch.as_tensor(out, device="cuda"),
+        torch.as_tensor(y, device="cuda"),
+        torch.as_tensor(scaler.scale_.astype("float32"), device="cuda"),
+        torch.as_tensor(scaler.min_.astype("float32"), device="cuda"),
+        torch.as_tensor(thr, device="cuda") if with_thr else None,
+        agg,
+    )
+    assert ts.shape == (N, F) and tu.shape == (N, F)
+    assert tots.shape == (N,) and totu.shape == (N,)
+    np.testing.assert_allclose(ts.cpu().numpy(), ts_ref, rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(tots.cpu().numpy(), tots_ref, rtol=1e-5,
+                               atol=1e-6)
+    np.testing.assert_allclose(tu.cpu().numpy(), tu_ref, rtol=1e-6, atol=1e-7)
+    np.testing.assert_allclose(totu.cpu().numpy(), totu_ref, rtol=1e-5,
+                               atol=1e-7)
+    if with_thr:
+        np.testing.assert_allclose(conf.cpu().numpy(), tu_ref / thr,
+                                   rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(tconf.cpu().numpy(), tots_ref / agg,
+                                   rtol=1e-5, atol=1e-6)
+    else:
+        assert conf.numel() == 0 and tconf.numel() == 0
+
+
 def test_anomaly_frame_device_path_matches_pandas():
     """DiffBased.anomaly at >=512 rows takes the fused kernel path; the
     frame must equal the pandas path bitwise-close."""
@@ -344,8 +469,12 @@ def test_anomaly_frame_device_path_matches_pandas():
     (1, 64, 10, 64, False),    # HF=4
 ])
 def test_lstm_seq_v2_vs_reference(G, B, T, H, last_only):
-    """The v2 (register-resident, H%16==0) scan kernels vs the
-    per-timestep fp32 oracle — same harness as the v1 test."""
+    """H % 16 == 0 shapes through the public dispatch vs the
+    per-timestep fp32 oracle — same harness as the v1 test. At these
+    grids (G * ceil(B/64) < 256) the dispatch does NOT take the v2
+    kernels: the forward runs the pipelined v3 kernel and the backward
+    the 16-byte pipelined kernel, as the launch record asserts. The v2
+    kernels are covered by test_lstm_scan_arms_gpu.py."""
     require_hip()
     H4 = 4 * H
     xW = _rand(G, B, T, H4, seed=40)
@@ -364,6 +493,7 @@ def test_lstm_seq_v2_vs_reference(G, B, T, H, last_only):
         ga_ref[:, :, t] = ga
 
     got_hs, got_cs, got_ga = ops.lstm_seq_fwd(to_dev_bf16(xW), to_dev_bf16(Wh))
+    assert ops.last_scan_launch()["family"] == "fwd_v3"
     torch.testing.assert_close(got_hs.float().cpu(), hs_ref, rtol=5e-2,
                                atol=3e-2)
     torch.testing.assert_close(got_cs.cpu(), cs_ref, rtol=5e-2, atol=3e-2)
@@ -387,6 +517,10 @@ def test_lstm_seq_v2_vs_reference(G, B, T, H, last_only):
 
     got_dG = ops.lstm_seq_bwd(to_dev_bf16(dSeq), got_ga, got_cs,
                               to_dev_bf16(Wh), last_only)
+    launch = ops.last_scan_launch()
+    assert (launch["family"], launch["has_dx"], launch["last_only"]) == (
+        "bwd_pipe", False, last_only
+    )
     torch.testing.assert_close(got_dG.float().cpu(), dG_ref, rtol=8e-2,
                                atol=4e-2)
 
@@ -560,20 +694,29 @@ def test_grouped_wgrad_hprev_matches_concat(G, B, T, H, N4):
     torch.testing.assert_close(got_b, want_b, rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("F", [50, 7])  # 16B-vector path and scalar path
+# F % 8 == 0 (8, 56) takes the 16-byte vector path, 50 and 7 the scalar
+# loop
+@pytest.mark.parametrize("F", [8, 56, 50, 7])
 def test_window_gather_matches_torch(F):
-    """K7 dedicated featurizer kernel vs the torch gather reference."""
+    """K7 dedicated featurizer kernel vs the torch gather reference,
+    including the first (idx = 0) and last (idx = N - T) windows. At
+    T = 256 with F = 8 or 56, T * F is a multiple of the 256 * 8
+    elements one 16-byte sweep of the workgroup covers; at T = 144 it
+    is not."""
     require_hip()
-    G, N, B, T = 3, 500, 40, 144
+    G, N, B = 3, 500, 40
     X = to_dev_bf16(_rand(G, N, F, seed=70))
-    idx = torch.randint(0, N - T + 1, (G, B), device="cuda",
-                        dtype=torch.int32)
-    got = ops.window_gather(X, idx, T)
-    rows = idx.long().unsqueeze(-1) + torch.arange(T, device="cuda")
-    want = X.gather(
-        1, rows.reshape(G, B * T, 1).expand(G, B * T, F)
-    ).view(G, B, T, F)
-    assert torch.equal(got, want)
+    for T in (144, 256):
+        idx = torch.randint(0, N - T + 1, (G, B), device="cuda",
+                            dtype=torch.int32)
+        idx[:, 0] = 0
+        idx[:, 1] = N - T
+        got = ops.window_gather(X, idx, T)
+        rows = idx.long().unsqueeze(-1) + torch.arange(T, device="cuda")
+        want = X.gather(
+            1, rows.reshape(G, B * T, 1).expand(G, B * T, F)
+        ).view(G, B, T, F)
+        assert torch.equal(got, want)
 
 
 def test_lstm_scan_row_tiles_bit_equal(monkeypatch):
