@@ -118,6 +118,13 @@ def trail_min_max(x, w: int):
     NaN-skipping max. Exact-equivalence tested in
     tests/test_packed.py::test_trail_min_max_matches_pandas.
 
+    NaN follows pandas' ``min_periods = w``: a window holding any NaN
+    is excluded, and a column without a valid window gives NaN. The
+    min filter alone would step over NaN, so it runs on the data with
+    NaN replaced by +inf and the windows a maximum filter finds in the
+    NaN mask are dropped before the max (still O(n)). +-inf are
+    ordinary values (tests/test_threshold_oracle.py).
+
     >>> import numpy as np, pandas as pd
     >>> a = np.array([5.0, 1.0, 4.0, 2.0, 8.0, 0.5])
     >>> float(trail_min_max(a, 3))
@@ -131,5 +138,15 @@ def trail_min_max(x, w: int):
     x = np.asarray(x)
     if x.shape[0] < w:
         return np.nan if x.ndim == 1 else np.full(x.shape[1], np.nan)
-    mf = minimum_filter1d(x, size=w, axis=0, mode="nearest", origin=(w - 1) // 2)
-    return mf[w - 1:].max(axis=0)
+    trailing = dict(size=w, axis=0, mode="nearest", origin=(w - 1) // 2)
+    nan = np.isnan(x)
+    if not nan.any():
+        return minimum_filter1d(x, **trailing)[w - 1:].max(axis=0)
+    from scipy.ndimage import maximum_filter1d
+
+    mf = minimum_filter1d(np.where(nan, np.inf, x), **trailing)[w - 1:]
+    bad = maximum_filter1d(nan.astype(np.uint8), **trailing)[w - 1:] > 0
+    # validity is tracked apart from the value: a column of -inf is -inf
+    out = np.where(bad, -np.inf, mf).max(axis=0)
+    out = np.where(bad.all(axis=0), np.nan, out)
+    return out[()] if x.ndim == 1 else out

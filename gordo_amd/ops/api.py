@@ -434,8 +434,10 @@ def row_quantile(X, q: float):
         return _require_hip().row_quantile(X, float(q))
     import numpy as _np
 
+    # in double: on fp32 input numpy forms the position q*(n-1) in fp32
     return torch.as_tensor(
-        _np.nanquantile(X.numpy(), float(q), axis=1), dtype=torch.float32
+        _np.nanquantile(X.numpy().astype(_np.float64), float(q), axis=1),
+        dtype=torch.float32,
     )
 
 

@@ -4,6 +4,8 @@ CPU/fp32 reference implementations of every device op.
 These are the numerics oracles: each HIP kernel in ``csrc/`` is tested
 against the same-named function here (tests/test_ops_gpu.py), and they
 are the execution path on hosts without a GPU (the CPU test lane).
+The LSTM scan and threshold-statistics oracles further down compute
+in fp64 and are test-only.
 
 Layouts (G = models in the pack, B = rows, In/Out = features):
     X   [G, B, In]
@@ -440,3 +442,112 @@ def lstm_seq_bwd_ref(dSeq, gacts, cs, Wh, last_only, *, Wx=None,
     if WxT is None:
         return torch.stack(dG, 2)
     return torch.stack(dG, 2), torch.stack(dX, 2)
+
+
+# ---------------------------------------------------------------------------
+# Threshold statistics (K10 trail_min_max, K11 windowed_quantile, K12
+# row_quantile; csrc/thresholds.hip). fp64 oracles written from the
+# definitions as plain per-window loops: no pandas rolling, numpy
+# quantile routines or scipy filters, so the tests can validate them
+# against those (tests/test_threshold_oracle.py). Inputs are [R, N]
+# (numpy or torch, any float dtype); outputs are numpy fp64.
+# ---------------------------------------------------------------------------
+def _as_f64_rows(X):
+    import numpy as np
+
+    if isinstance(X, torch.Tensor):
+        X = X.detach().cpu().to(torch.float64).numpy()
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X must be [R, N]")
+    return X
+
+
+def _interp_ref(sorted_valid, q):
+    """'linear' quantile of an ascending NaN-free sequence: position
+    ``q * (n - 1)`` in double, interpolated between the two
+    neighbouring order statistics. Returns ``(value, s_lo, s_hi)``;
+    all NaN for an empty sequence."""
+    n = len(sorted_valid)
+    if n == 0:
+        return math.nan, math.nan, math.nan
+    pos = float(q) * (n - 1)
+    lo = int(math.floor(pos))
+    hi = lo + 1 if lo + 1 < n else lo
+    frac = pos - lo
+    s_lo, s_hi = float(sorted_valid[lo]), float(sorted_valid[hi])
+    if s_lo == s_hi:  # also keeps inf - inf out of the expression
+        return s_lo, s_lo, s_hi
+    return s_lo + (s_hi - s_lo) * frac, s_lo, s_hi
+
+
+def trail_min_max_ref(X, w: int):
+    """K10: per row, the maximum over all full trailing windows of the
+    window minimum (``rolling(w).min().max()``). A window holding any
+    NaN is excluded; a row with no valid window (or ``N < w``) gives
+    NaN."""
+    import numpy as np
+
+    X = _as_f64_rows(X)
+    R, N = X.shape
+    out = np.full(R, np.nan)
+    for r in range(R):
+        best = None
+        for i in range(w - 1, N):
+            win = X[r, i - w + 1:i + 1]
+            if np.isnan(win).any():
+                continue
+            m = win.min()
+            if best is None or m > best:
+                best = m
+        if best is not None:
+            out[r] = best
+    return out
+
+
+def windowed_quantile_ref(X, w: int, q: float, return_neighbours=False):
+    """K11: per row ``rolling(w).quantile(q)`` with ``min_periods = w``
+    (any NaN in a window gives NaN), 'linear' interpolation; output
+    columns are the windows ending at ``w-1 .. N-1``. With
+    ``return_neighbours`` also returns the order statistics ``s_lo``,
+    ``s_hi`` each value was interpolated between."""
+    import numpy as np
+
+    X = _as_f64_rows(X)
+    R, N = X.shape
+    if w < 1 or w > N:
+        raise ValueError("window longer than series")
+    no = N - w + 1
+    out = np.full((R, no), np.nan)
+    s_lo = np.full((R, no), np.nan)
+    s_hi = np.full((R, no), np.nan)
+    for r in range(R):
+        for i0 in range(no):
+            win = X[r, i0:i0 + w]
+            if np.isnan(win).any():
+                continue
+            out[r, i0], s_lo[r, i0], s_hi[r, i0] = _interp_ref(
+                np.sort(win), q
+            )
+    if return_neighbours:
+        return out, s_lo, s_hi
+    return out
+
+
+def row_quantile_ref(X, q: float, return_neighbours=False):
+    """K12: per row quantile over the non-NaN values, 'linear'
+    interpolation; a row without valid values gives NaN."""
+    import numpy as np
+
+    X = _as_f64_rows(X)
+    R = X.shape[0]
+    out = np.full(R, np.nan)
+    s_lo = np.full(R, np.nan)
+    s_hi = np.full(R, np.nan)
+    for r in range(R):
+        row = X[r]
+        valid = np.sort(row[~np.isnan(row)])
+        out[r], s_lo[r], s_hi[r] = _interp_ref(valid, q)
+    if return_neighbours:
+        return out, s_lo, s_hi
+    return out
