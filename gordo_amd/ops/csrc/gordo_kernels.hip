@@ -25,6 +25,7 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include <cstdint>
 #include <vector>
 
 #define DEV_INLINE __device__ __forceinline__
@@ -113,7 +114,12 @@ template <int BMODE, bool ACC, bool FUSE_BIAS_ACT>
 __global__ __launch_bounds__(256) void grouped_gemm_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     const float* __restrict__ bias, bf16* __restrict__ C,
-    int M, int N, int K, int act, int mt, int nt, int nblocks) {
+    int M, int N, int K, int act, int mt, int nt, int nblocks, int vecA,
+    int vecB) {
+  // vecA / vecB: the host's verdict on the 16-byte staging of A and of
+  // B (BMODE_NK): K % 8 == 0 AND a 16-byte aligned base pointer. K
+  // alone is not enough: callers pass offset views of a flat bf16
+  // buffer, whose base can sit at any even byte.
   __shared__ bf16 sm[2 * BM * LDT];
   bf16* As = sm;               // [BM][LDT]
   bf16* Bs = sm + BM * LDT;    // [BN][LDT]  (Bt: [n][k])
@@ -143,10 +149,10 @@ __global__ __launch_bounds__(256) void grouped_gemm_kernel(
       int kk = (tid & 3) * 8;
       int gm = m0 + row;
       bf16 v[8];
-      if ((K & 7) == 0 && gm < M && k0 + kk + 8 <= K) {
-        // K 8-aligned => every row's 8-element k-slice is one 16-byte
-        // naturally-aligned global load (guide G13; the scalar loop
-        // below is the unaligned-K fallback)
+      if (vecA && gm < M && k0 + kk + 8 <= K) {
+        // K 8-aligned on a 16-byte aligned base => every row's
+        // 8-element k-slice is one 16-byte naturally-aligned global
+        // load (guide G13; the scalar loop below is the fallback)
         *reinterpret_cast<bf16x8*>(v) = *reinterpret_cast<const bf16x8*>(
             &Ag[(size_t)gm * K + k0 + kk]);
       } else {
@@ -177,7 +183,7 @@ __global__ __launch_bounds__(256) void grouped_gemm_kernel(
       int kk = (tid & 3) * 8;
       int gn = n0 + n;
       bf16 v[8];
-      if ((K & 7) == 0 && gn < N && k0 + kk + 8 <= K) {
+      if (vecB && gn < N && k0 + kk + 8 <= K) {
         *reinterpret_cast<bf16x8*>(v) = *reinterpret_cast<const bf16x8*>(
             &Bg[(size_t)gn * K + k0 + kk]);
       } else {
@@ -434,13 +440,14 @@ __global__ __launch_bounds__(256) void grouped_wgrad_kernel(
 // K7 — sliding-window featurizer: gather lookback
 // windows [G, B, T, F] straight out of the resident series [G, N, F].
 // One workgroup per (g, window); lanes stream the T*F window elements
-// with 16-byte loads when the feature row is 8-aligned (bf16 x 8).
+// with 16-byte loads when the feature row is 8-aligned (bf16 x 8) and
+// X and out are 16-byte aligned (`vec`, decided on the host).
 // The device analog of create_keras_timeseriesgenerator
 // (reference gordo/machine/model/models.py:713-793).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void window_gather_kernel(
     const bf16* __restrict__ X, const int* __restrict__ idx,
-    bf16* __restrict__ out, int N, int F, int B, int T) {
+    bf16* __restrict__ out, int N, int F, int B, int T, int vec) {
   const int g = blockIdx.x / B;
   const int b = blockIdx.x % B;
   const int start = idx[(size_t)g * B + b];
@@ -448,7 +455,7 @@ __global__ __launch_bounds__(256) void window_gather_kernel(
   bf16* dst = out + (((size_t)g * B + b) * T) * F;
   const size_t n = (size_t)T * F;
   const int tid = threadIdx.x;
-  if ((F & 7) == 0) {
+  if (vec) {  // F % 8 == 0, X and out 16-byte aligned (host-checked)
     const bf16x8* s8 = reinterpret_cast<const bf16x8*>(src);
     bf16x8* d8 = reinterpret_cast<bf16x8*>(dst);
     for (size_t i = tid; i < n / 8; i += 256) d8[i] = s8[i];
@@ -615,6 +622,16 @@ hipStream_t cur_stream() {
   return at::cuda::getCurrentCUDAStream().stream();
 }
 
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// 16-byte staging of a row-major [.., rows, K] bf16 operand is legal
+// only when every row start is 16-byte aligned: K % 8 == 0 and an
+// aligned base (a contiguous bf16 VIEW passes through to_bf16c
+// unchanged, storage offset included).
+int vec16_ok(const torch::Tensor& t, int K) {
+  return (K % 8 == 0 && aligned16(t.data_ptr())) ? 1 : 0;
+}
+
 torch::Tensor grouped_linear_fwd(torch::Tensor X, torch::Tensor W,
                                  torch::Tensor b, int64_t act) {
   CHECK_GPU(X);
@@ -630,7 +647,7 @@ torch::Tensor grouped_linear_fwd(torch::Tensor X, torch::Tensor W,
                      dim3(256), 0, cur_stream(),
                      (const bf16*)Xc.data_ptr(), (const bf16*)Wc.data_ptr(),
                      bc.data_ptr<float>(), (bf16*)Y.data_ptr(), M, N, K,
-                     (int)act, mt, nt, nblocks);
+                     (int)act, mt, nt, nblocks, vec16_ok(Xc, K), 0);
   return Y;
 }
 
@@ -649,7 +666,7 @@ torch::Tensor grouped_linear_bwd_data(torch::Tensor dZ, torch::Tensor W) {
                      dim3(256), 0, cur_stream(),
                      (const bf16*)Zc.data_ptr(), (const bf16*)Wc.data_ptr(),
                      nullptr, (bf16*)dX.data_ptr(), M, Kout, N, ACT_LINEAR,
-                     mt, nt, nblocks);
+                     mt, nt, nblocks, vec16_ok(Zc, N), vec16_ok(Wc, N));
   return dX;
 }
 
@@ -667,7 +684,7 @@ torch::Tensor grouped_gemm_acc(torch::Tensor A, torch::Tensor B,
                      dim3(256), 0, cur_stream(),
                      (const bf16*)Ac.data_ptr(), (const bf16*)Bc.data_ptr(),
                      nullptr, (bf16*)C.data_ptr(), M, N, K, ACT_LINEAR, mt,
-                     nt, nblocks);
+                     nt, nblocks, vec16_ok(Ac, K), 0);
   return C;
 }
 
@@ -775,7 +792,8 @@ torch::Tensor window_gather(torch::Tensor X, torch::Tensor idx,
   hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)G * B),
                      dim3(256), 0, cur_stream(),
                      (const bf16*)Xc.data_ptr(), ic.data_ptr<int>(),
-                     (bf16*)out.data_ptr(), N, F, B, (int)T);
+                     (bf16*)out.data_ptr(), N, F, B, (int)T,
+                     (vec16_ok(Xc, F) && aligned16(out.data_ptr())) ? 1 : 0);
   return out;
 }
 

@@ -5,7 +5,8 @@ These are the numerics oracles: each HIP kernel in ``csrc/`` is tested
 against the same-named function here (tests/test_ops_gpu.py), and they
 are the execution path on hosts without a GPU (the CPU test lane).
 The LSTM scan and threshold-statistics oracles further down compute
-in fp64 and are test-only.
+in fp64 and are test-only, as are the ``*_ref`` oracles of the grouped
+GEMM and pointwise training ops at the end.
 
 Layouts (G = models in the pack, B = rows, In/Out = features):
     X   [G, B, In]
@@ -551,3 +552,161 @@ def row_quantile_ref(X, q: float, return_neighbours=False):
     if return_neighbours:
         return out, s_lo, s_hi
     return out
+
+
+# ---------------------------------------------------------------------------
+# Grouped GEMM and pointwise training ops: fp64 oracles written from
+# the definitions (explicit sums over the contracted index, no bmm), so
+# tests/test_gemm_oracle.py can validate them against torch.bmm and
+# autograd. Callers pass the kernel's view of the inputs: operands
+# already rounded to bf16 (any float dtype holding those values), fp32
+# for bias, c, dc and the optimizer state. Every oracle returns
+# ``(want, emu)``: the fp64 value and the same computation carried out
+# in fp32 on the CPU. ``|emu - want|`` measures what fp32 arithmetic
+# alone costs at that shape, which is what the tests scale their
+# absolute tolerance from. Test-only, like the scan oracles above.
+# ---------------------------------------------------------------------------
+def _contract(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """sum_k A[g, m, k] * B[g, k, n], one k at a time."""
+    out = torch.zeros(A.shape[0], A.shape[1], B.shape[2], dtype=A.dtype)
+    for k in range(A.shape[2]):
+        out += A[:, :, k:k + 1] * B[:, k:k + 1, :]
+    return out
+
+
+def _both(fn):
+    """(fn in fp64, fn in fp32)."""
+    return fn(torch.float64), fn(torch.float32)
+
+
+def grouped_linear_fwd_ref(X, W, b, act):
+    """act(sum_k X[g,m,k] W[g,k,n] + b[g,n])."""
+    act = act_code(act)
+
+    def run(dt):
+        z = _contract(X.to(dt), W.to(dt)) + b.to(dt).unsqueeze(1)
+        return apply_act(z, act)
+
+    return _both(run)
+
+
+def grouped_linear_bwd_data_ref(dZ, W):
+    """dX[g,m,k] = sum_n dZ[g,m,n] W[g,k,n]."""
+    return _both(
+        lambda dt: _contract(dZ.to(dt), W.to(dt).transpose(1, 2).contiguous())
+    )
+
+
+def grouped_gemm_acc_ref(A, B, C0):
+    """C0[g,m,n] + sum_k A[g,m,k] B[g,k,n] (C0 holds bf16 values)."""
+    return _both(lambda dt: C0.to(dt) + _contract(A.to(dt), B.to(dt)))
+
+
+def act_l1_bwd_ref(dA, Y, act, l1):
+    """(dA + l1 sign(Y)) act'(Y), act' from the output; sign(±0) = 0
+    and relu'(±0) = 0. ``l1`` is used as the fp32 value the kernel
+    receives."""
+    act = act_code(act)
+    l1 = float(torch.tensor(l1, dtype=torch.float32))
+
+    def run(dt):
+        y, g = Y.to(dt), dA.to(dt)
+        if l1 != 0.0:
+            g = g + l1 * torch.sign(y)
+        return g * act_grad_from_output(y, act)
+
+    return _both(run)
+
+
+def mse_bwd_ref(Y, T, real_n: int = -1):
+    """loss[g] = sum (Y-T)^2 / n, dY = 2 (Y-T) / n over each model's
+    elements; n = ``real_n`` if positive, else the per-model count.
+    Returns ``((loss, dY) fp64, (loss, dY) fp32)``. The fp32 loss is a
+    plain left-to-right running sum in fp32 (numpy ``add.accumulate``
+    keeps the dtype; torch's CPU sums are pairwise or accumulate in
+    double), the order-free worst case a reduction tree improves on."""
+    import numpy as np
+
+    G = Y.shape[0]
+    n = Y[0].numel() if real_n <= 0 else int(real_n)
+
+    def run(dt):
+        d = (Y.to(dt) - T.to(dt)).reshape(G, -1)
+        inv = torch.tensor(1.0, dtype=dt) / n
+        sq = d * d
+        if dt == torch.float32:
+            total = torch.from_numpy(
+                np.add.accumulate(sq.numpy(), axis=1, dtype=np.float32)[:, -1]
+                .copy()
+            )
+        else:
+            total = sq.sum(dim=1)
+        return total * inv, (2.0 * d * inv).reshape(Y.shape)
+
+    return _both(run)
+
+
+def lstm_pointwise_fwd_ref(gates, c_prev):
+    """One LSTM cell step from pre-activations [.., 4H] (order i, f,
+    g, o) and c_prev [.., H]: ``((h, c, gact) fp64, (...) fp32)``,
+    nothing rounded to bf16."""
+    H = gates.shape[-1] // 4
+
+    def run(dt):
+        z, cp = gates.to(dt), c_prev.to(dt)
+        i = 1.0 / (1.0 + torch.exp(-z[..., 0 * H:1 * H]))
+        f = 1.0 / (1.0 + torch.exp(-z[..., 1 * H:2 * H]))
+        g = torch.tanh(z[..., 2 * H:3 * H])
+        o = 1.0 / (1.0 + torch.exp(-z[..., 3 * H:4 * H]))
+        c = f * cp + i * g
+        return o * torch.tanh(c), c, torch.cat([i, f, g, o], dim=-1)
+
+    return _both(run)
+
+
+def lstm_pointwise_bwd_ref(dh, dc_next, gact, c, c_prev):
+    """Gradient of that step with respect to the pre-activations and
+    c_prev, from the ACTIVATED gates as given (the kernel reads them
+    back as bf16): ``((dgates, dc_prev) fp64, (...) fp32)``."""
+    H = dh.shape[-1]
+
+    def run(dt):
+        ga = gact.to(dt)
+        i, f = ga[..., 0 * H:1 * H], ga[..., 1 * H:2 * H]
+        g, o = ga[..., 2 * H:3 * H], ga[..., 3 * H:4 * H]
+        d, cc, cp = dh.to(dt), c.to(dt), c_prev.to(dt)
+        tc = torch.tanh(cc)
+        dc = dc_next.to(dt) + d * o * (1.0 - tc * tc)
+        dgates = torch.cat([
+            dc * g * i * (1.0 - i),
+            dc * cp * f * (1.0 - f),
+            dc * i * (1.0 - g * g),
+            d * tc * o * (1.0 - o),
+        ], dim=-1)
+        return dgates, dc * f
+
+    return _both(run)
+
+
+def adam_step_ref(p, g, m, v, lr, beta1, beta2, eps, step):
+    """One Adam step (Keras: m̂ = m/(1-β1^t), v̂ = v/(1-β2^t),
+    p -= lr m̂ / (sqrt(v̂) + eps)) from fp32 p, g, m, v, out of place.
+    The hyper-parameters are taken as the fp32 values the kernel
+    receives. Returns ``((p, m, v) fp64, (p, m, v) fp32)``."""
+    lr, beta1, beta2, eps = (
+        float(torch.tensor(x, dtype=torch.float32))
+        for x in (lr, beta1, beta2, eps)
+    )
+
+    def run(dt):
+        b1, b2 = (torch.tensor(x, dtype=dt) for x in (beta1, beta2))
+        gg = g.to(dt)
+        m1 = b1 * m.to(dt) + (1.0 - b1) * gg
+        v1 = b2 * v.to(dt) + (1.0 - b2) * gg * gg
+        bc1 = 1.0 - b1 ** int(step)
+        bc2 = 1.0 - b2 ** int(step)
+        lr_t = torch.tensor(lr, dtype=dt)
+        p1 = p.to(dt) - lr_t / bc1 * m1 / (torch.sqrt(v1 / bc2) + eps)
+        return p1, m1, v1
+
+    return _both(run)

@@ -10,6 +10,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from gemm_cases import check_wgrad as _check_wgrad
+from gemm_cases import wgrad_oracle as _wgrad_oracle
 from gordo_amd import ops
 from gordo_amd.ops import reference as ref
 
@@ -106,33 +108,6 @@ def test_grouped_linear_wgrad(G, M, K, N):
     tol = dict(rtol=3e-2, atol=2e-2 * max(1.0, (M / 256) ** 0.5))
     torch.testing.assert_close(gotW.cpu(), wantW, **tol)
     torch.testing.assert_close(gotb.cpu(), wantb, **tol)
-
-
-def _wgrad_oracle(A, dZ):
-    """fp64 bmm on the bf16-rounded inputs, and the bound the kernel's
-    fp32 result must keep against it: 4x the error of the same product
-    in fp32 on the CPU, floored at 2 ulps of the fp32 output."""
-    A, dZ = (t.to(torch.bfloat16).double() for t in (A, dZ))
-    want_W = torch.bmm(A.transpose(1, 2), dZ)
-    want_b = dZ.sum(dim=1)
-    emu_W = torch.bmm(A.float().transpose(1, 2), dZ.float())
-    emu_b = dZ.float().sum(dim=1)
-    atol_W = 4 * (emu_W.double() - want_W).abs().max().item()
-    atol_b = 4 * (emu_b.double() - want_b).abs().max().item()
-    return (want_W, atol_W), (want_b, atol_b)
-
-
-def _check_wgrad(name, got, want_atol):
-    want, atol = want_atol
-    assert got.dtype == torch.float32
-    err = (got.double().cpu() - want).abs()
-    bound = torch.clamp(2.0 ** -22 * want.abs(), min=atol)
-    print(f"{name}: max abs err {err.max().item():.3e}, atol {atol:.3e}, "
-          f"scale {want.abs().max().item():.3e}")
-    assert bool((err <= bound).all()), (
-        f"{name}: max err {err.max().item():.3e} beyond "
-        f"max({atol:.3e}, 2^-22 |want|)"
-    )
 
 
 @pytest.mark.parametrize(
