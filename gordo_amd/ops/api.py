@@ -124,6 +124,20 @@ def grouped_wgrad_xh(seq, hs, dZ, T: int):
     return dWx, dWh, db
 
 
+def last_wgrad_launch() -> dict:
+    """Which weight-grad kernel this thread's last ``grouped_wgrad_xh``
+    / ``grouped_linear_wgrad`` / ``grouped_linear_wgrad_hprev`` call
+    launched: ``family`` ("wgrad_pipe": the whole-tile kernel with
+    16-byte loads and transposed LDS reads; "wgrad_tile": the 64x64
+    tile kernel), ``chunks`` (M-chunks, i.e. ``gridDim.y``; more than
+    one means fp32 atomics into dW) and ``mstep`` (rows per step).
+    Host-side record; ``family`` is "" before any launch.
+    ``GORDO_WGRAD_PIPE=0`` forces "wgrad_tile"; ``GORDO_WGRAD_CHUNK``
+    forces the chunk length in rows."""
+    family, chunks, mstep = _require_hip().last_wgrad_launch()
+    return {"family": family, "chunks": chunks, "mstep": mstep}
+
+
 def grouped_gemm_acc(A, B, C):
     if _on_gpu(A):
         return _require_hip().grouped_gemm_acc(A, B, C)

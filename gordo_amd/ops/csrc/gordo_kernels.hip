@@ -26,6 +26,9 @@
 #include <ATen/cuda/CUDAContext.h>
 
 #include <cstdint>
+#include <cstdlib>
+#include <string>
+#include <tuple>
 #include <vector>
 
 #define DEV_INLINE __device__ __forceinline__
@@ -289,41 +292,12 @@ __global__ __launch_bounds__(256) void grouped_wgrad_kernel(
   f32x4 acc[2][2] = {};
   float db_part = 0.f;
 
-  // Vectorized transpose staging (row-contiguous 16-byte loads +
-  // scalar LDS-transposed writes) MEASURED SLOWER than the legacy
-  // column gather at the fleet shape (0.288 vs 0.254 ms at
-  // M=36864 K=56 N=192 G=31 — gpurun r2_call10): the column gather's
-  // lane pattern already coalesces into 4x32B segments per
-  // instruction, while 8 ds_write_b16 per thread cost more LDS issue
-  // than the loads saved. Kept compiled-out for future re-tuning.
-  constexpr bool vecA = false;
-  constexpr bool vecZ = false;
-  (void)0;
+  // Both stagings are column gathers (8 rows at one k / one n per
+  // thread). The 16-byte row-load + ds_write_b16 transpose variant
+  // measured slower (docs/kernels.md, "Whole-tile weight-grad").
   for (int m0 = m_begin; m0 < m_end; m0 += BK) {
     // stage A[m0..+32][k0..+64] transposed into As[k][m]
-    if (vecA) {
-      int m = tid >> 3;           // 0..31
-      int kk8 = (tid & 7) * 8;    // 0..56
-      int gm = m0 + m;
-      int gk0 = k0 + kk8;
-      bool ok = gm < M;
-      size_t row = (size_t)gm;
-      if (tshiftT > 0) {
-        ok = ok && (gm % tshiftT) > 0;  // t == 0 -> h_prev is zero
-        row = (size_t)gm - 1;
-      }
-      bf16 v[8];
-      if (ok && gk0 + 8 <= K) {
-        *reinterpret_cast<bf16x8*>(v) =
-            *reinterpret_cast<const bf16x8*>(&Ag[row * K + gk0]);
-      } else {
-        #pragma unroll
-        for (int e = 0; e < 8; ++e)
-          v[e] = (ok && gk0 + e < K) ? Ag[row * K + gk0 + e] : f2bf(0.f);
-      }
-      #pragma unroll
-      for (int e = 0; e < 8; ++e) As[(kk8 + e) * LDT + m] = v[e];
-    } else {
+    {
       int k = tid >> 2;           // 0..63
       int mm = (tid & 3) * 8;     // 0..24
       int gk = k0 + k;
@@ -349,34 +323,7 @@ __global__ __launch_bounds__(256) void grouped_wgrad_kernel(
     // stage dZ[m0..+32][n0..+64] transposed into Zs[n][m]; k-tile-0
     // blocks fold the bias-grad column sum into the same pass (what a
     // separate colsum kernel did with a latency-bound column walk).
-    if (vecZ) {
-      int m = tid >> 3;
-      int nn8 = (tid & 7) * 8;
-      int gm = m0 + m;
-      int gn0 = n0 + nn8;
-      bf16 v[8];
-      if (gm < M && gn0 + 8 <= N) {
-        *reinterpret_cast<bf16x8*>(v) =
-            *reinterpret_cast<const bf16x8*>(&Zg[(size_t)gm * N + gn0]);
-      } else {
-        #pragma unroll
-        for (int e = 0; e < 8; ++e)
-          v[e] = (gm < M && gn0 + e < N) ? Zg[(size_t)gm * N + gn0 + e]
-                                         : f2bf(0.f);
-      }
-      #pragma unroll
-      for (int e = 0; e < 8; ++e) Zs[(nn8 + e) * LDT + m] = v[e];
-      if (k0 == 0) {
-        // bias-grad partials from LDS after the transpose (the legacy
-        // in-flight accumulation had per-n thread ownership)
-        __syncthreads();
-        int n = tid >> 2;
-        int mm = (tid & 3) * 8;
-        #pragma unroll
-        for (int e = 0; e < 8; ++e)
-          db_part += bf2f(Zs[n * LDT + mm + e]);
-      }
-    } else {
+    {
       int n = tid >> 2;
       int mm = (tid & 3) * 8;
       int gn = n0 + n;
@@ -605,6 +552,15 @@ __global__ void lstm_pw_bwd_kernel(
   }
 }
 
+// whole-tile weight-grad kernel (wgrad_pipe.hip)
+namespace gordo_wgrad {
+constexpr int MSTEP = 32;  // rows of M per step
+bool pipe_shape_ok(int K, int K1, int N);
+void launch_pipe(const void* A1, const void* A2, const void* dZ, float* dW,
+                 float* db, int G, int M, int N, int K, int K1, int T,
+                 int mchunk, int nchunks, hipStream_t stream);
+}  // namespace gordo_wgrad
+
 // ---------------------------------------------------------------------------
 // Host-side launchers (torch extension API)
 // ---------------------------------------------------------------------------
@@ -688,6 +644,104 @@ torch::Tensor grouped_gemm_acc(torch::Tensor A, torch::Tensor B,
   return C;
 }
 
+// ---- weight-grad dispatch ----
+// wgrad_pipe (wgrad_pipe.hip): whole-[K,N]-tile kernel, 16-byte loads,
+// transposed LDS reads. wgrad_tile: grouped_wgrad_kernel above.
+struct WgradLaunch {
+  const char* family = "";
+  int chunks = 0;
+  int mstep = 0;
+};
+thread_local WgradLaunch g_last_wgrad;
+
+// GORDO_WGRAD_PIPE=0 (read per call) restores grouped_wgrad_kernel
+// everywhere.
+inline bool wgrad_pipe_enabled() {
+  const char* e = getenv("GORDO_WGRAD_PIPE");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
+// GORDO_WGRAD_CHUNK=<rows> (read per call) forces the M-chunk length of
+// either kernel, rounded up to whole m-steps: a test and A/B knob.
+inline int wgrad_forced_chunk() {
+  if (const char* e = getenv("GORDO_WGRAD_CHUNK")) {
+    int r = atoi(e);
+    if (r > 0) return r;
+  }
+  return 0;
+}
+
+// The whole-tile kernel's grid is one workgroup per (model, chunk). It
+// aims for at most 512 = 2 per CU, the residency of the largest
+// instantiations, so the grid is one wave of workgroups without a tail:
+// 16 chunks at G = 31 and 8 at G = 62 measured fastest (BASELINE.md,
+// "Whole-tile weight-grad"). Chunks shorter than 512 rows cost more in
+// atomics and zero-fill than they gain (same section, M = 3456 row).
+// No small-M threshold: the dense M = 256 shape is faster here too.
+constexpr int WGRAD_PIPE_TARGET_WGS = 512;
+constexpr int WGRAD_PIPE_MIN_CHUNK = 512;
+
+// A1 [G, M, K1] rows as-is (undefined when K1 == 0); A2 [G, M, K-K1]
+// read at row-1, zero where row % T == 0 (undefined when K1 == K).
+// Returns {dW [G, K, N], db [G, N]}.
+std::vector<torch::Tensor> wgrad_dispatch(const torch::Tensor& A1,
+                                          const torch::Tensor& A2,
+                                          const torch::Tensor& Zc, int G,
+                                          int M, int N, int K, int K1,
+                                          int T) {
+  const bool has1 = K1 > 0, has2 = K1 < K;
+  const void* p1 = has1 ? A1.data_ptr() : nullptr;
+  const void* p2 = has2 ? A2.data_ptr() : nullptr;
+  auto opts = Zc.options().dtype(torch::kFloat32);
+  auto db = torch::zeros({G, N}, opts);  // always atomically accumulated
+  const int forced = wgrad_forced_chunk();
+  const bool pipe = wgrad_pipe_enabled() &&
+                    gordo_wgrad::pipe_shape_ok(K, K1, N) &&
+                    (!has1 || aligned16(p1)) && (!has2 || aligned16(p2)) &&
+                    aligned16(Zc.data_ptr());
+  if (pipe) {
+    constexpr int MS = gordo_wgrad::MSTEP;
+    int target_chunks = std::max(1, WGRAD_PIPE_TARGET_WGS / std::max(G, 1));
+    int mchunk = forced > 0 ? forced
+                            : std::max(WGRAD_PIPE_MIN_CHUNK,
+                                       ceil_div(M, target_chunks));
+    mchunk = std::max(MS, ceil_div(mchunk, MS) * MS);
+    int nchunks = ceil_div(M, mchunk);
+    auto dW = nchunks > 1 ? torch::zeros({G, K, N}, opts)
+                          : torch::empty({G, K, N}, opts);
+    gordo_wgrad::launch_pipe(p1, p2, Zc.data_ptr(), dW.data_ptr<float>(),
+                             db.data_ptr<float>(), G, M, N, K, K1, T,
+                             mchunk, nchunks, cur_stream());
+    g_last_wgrad = WgradLaunch{"wgrad_pipe", nchunks, MS};
+    return {dW, db};
+  }
+  // the tile kernel takes (A, A2) as (first operand, optional second):
+  // a lone shifted operand travels as A with tshiftT = T
+  int kt = ceil_div(K, BM), nt = ceil_div(N, BN);
+  int nblocks = G * kt * nt;
+  // choose the M split so the grid comfortably fills 256 CUs
+  int target_chunks = std::max(1, 2048 / std::max(nblocks, 1));
+  int mchunk = forced > 0 ? forced : ceil_div(M, target_chunks);
+  mchunk = std::max(BK, ceil_div(mchunk, BK) * BK);
+  int nchunks = ceil_div(M, mchunk);
+  auto dW = nchunks > 1 ? torch::zeros({G, K, N}, opts)
+                        : torch::empty({G, K, N}, opts);
+  const bf16* a = (const bf16*)(has1 ? p1 : p2);
+  const bf16* a2 = (has1 && has2) ? (const bf16*)p2 : nullptr;
+  hipLaunchKernelGGL(grouped_wgrad_kernel, dim3(nblocks, nchunks),
+                     dim3(256), 0, cur_stream(), a,
+                     (const bf16*)Zc.data_ptr(), dW.data_ptr<float>(),
+                     db.data_ptr<float>(), M, N, K, kt, nt, nblocks, mchunk,
+                     has2 ? T : 0, a2, (has1 && has2) ? K1 : K);
+  g_last_wgrad = WgradLaunch{"wgrad_tile", nchunks, BK};
+  return {dW, db};
+}
+
+std::tuple<std::string, int, int> last_wgrad_launch() {
+  return {std::string(g_last_wgrad.family), g_last_wgrad.chunks,
+          g_last_wgrad.mstep};
+}
+
 std::vector<torch::Tensor> grouped_linear_wgrad_impl(torch::Tensor X,
                                                      torch::Tensor dZ,
                                                      int64_t tshiftT) {
@@ -698,24 +752,10 @@ std::vector<torch::Tensor> grouped_linear_wgrad_impl(torch::Tensor X,
   if (tshiftT > 0) {
     TORCH_CHECK(M % tshiftT == 0, "rows must be a multiple of T");
     TORCH_CHECK(Xc.numel() == (int64_t)G * M * K, "X/dZ row mismatch");
+    return wgrad_dispatch(torch::Tensor(), Xc, Zc, G, M, N, K, 0,
+                          (int)tshiftT);
   }
-  int kt = ceil_div(K, BM), nt = ceil_div(N, BN);
-  int nblocks = G * kt * nt;
-  // choose the M split so the grid comfortably fills 256 CUs
-  int target_chunks = std::max(1, 2048 / std::max(nblocks, 1));
-  int mchunk = std::max(BK, (int)(((M + target_chunks - 1) / target_chunks
-                                   + BK - 1) / BK * BK));
-  int nchunks = ceil_div(M, mchunk);
-  auto opts = Xc.options().dtype(torch::kFloat32);
-  auto dW = nchunks > 1 ? torch::zeros({G, K, N}, opts)
-                        : torch::empty({G, K, N}, opts);
-  auto db = torch::zeros({G, N}, opts);  // always atomically accumulated
-  hipLaunchKernelGGL(grouped_wgrad_kernel, dim3(nblocks, nchunks),
-                     dim3(256), 0, cur_stream(),
-                     (const bf16*)Xc.data_ptr(), (const bf16*)Zc.data_ptr(),
-                     dW.data_ptr<float>(), db.data_ptr<float>(), M, N, K,
-                     kt, nt, nblocks, mchunk, (int)tshiftT, nullptr, K);
-  return {dW, db};
+  return wgrad_dispatch(Xc, torch::Tensor(), Zc, G, M, N, K, K, 0);
 }
 
 std::vector<torch::Tensor> grouped_wgrad_xh(torch::Tensor seq,
@@ -731,24 +771,8 @@ std::vector<torch::Tensor> grouped_wgrad_xh(torch::Tensor seq,
   int G = Sc.size(0), M = Zc.size(1), F = Sc.size(2), H = Hc.size(2);
   int N = Zc.size(2);
   TORCH_CHECK(M % T == 0 && Hc.size(1) == M, "row/T mismatch");
-  int K = F + H;
-  int kt = ceil_div(K, BM), nt = ceil_div(N, BN);
-  int nblocks = G * kt * nt;
-  int target_chunks = std::max(1, 2048 / std::max(nblocks, 1));
-  int mchunk = std::max(BK, (int)(((M + target_chunks - 1) / target_chunks
-                                   + BK - 1) / BK * BK));
-  int nchunks = ceil_div(M, mchunk);
-  auto opts = Sc.options().dtype(torch::kFloat32);
-  auto dW = nchunks > 1 ? torch::zeros({G, K, N}, opts)
-                        : torch::empty({G, K, N}, opts);
-  auto db = torch::zeros({G, N}, opts);
-  hipLaunchKernelGGL(grouped_wgrad_kernel, dim3(nblocks, nchunks),
-                     dim3(256), 0, cur_stream(),
-                     (const bf16*)Sc.data_ptr(), (const bf16*)Zc.data_ptr(),
-                     dW.data_ptr<float>(), db.data_ptr<float>(), M, N, K,
-                     kt, nt, nblocks, mchunk, (int)T,
-                     (const bf16*)Hc.data_ptr(), F);
-  return {dW.narrow(1, 0, F), dW.narrow(1, F, H), db};
+  auto out = wgrad_dispatch(Sc, Hc, Zc, G, M, N, F + H, F, (int)T);
+  return {out[0].narrow(1, 0, F), out[0].narrow(1, F, H), out[1]};
 }
 
 std::vector<torch::Tensor> grouped_linear_wgrad(torch::Tensor X,
@@ -986,6 +1010,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "dW = X^T@dZ, db = colsum(dZ) per group (MFMA)");
   mod.def("grouped_linear_wgrad_hprev", &grouped_linear_wgrad_hprev,
           "dWh = h_prev^T@dG with in-kernel t-1 shift (no concat)");
+  mod.def("last_wgrad_launch", &last_wgrad_launch,
+          "(family, chunks, mstep) of this thread's last weight-grad "
+          "launch");
   mod.def("grouped_wgrad_xh", &grouped_wgrad_xh,
           "combined {dWx, dWh, db} — dZ staged once for both");
   mod.def("window_gather", &window_gather,
