@@ -49,8 +49,14 @@ def pad_enabled(device) -> bool:
     (GORDO_PAD8=0 disables): bf16x8 = 16 bytes unlocks vectorized
     global staging loads in every grouped GEMM (guide G13 — scalar
     bf16 staging is a 2-2.5x tax), and padded hidden units are
-    PROVABLY inert: zero weights + zero bias give g=tanh(0)=0 so
-    c=f*0+i*0=0 and h=o*tanh(0)=0 forever; all their gradients are
+    PROVABLY inert: zero weights + zero bias give g=φ(0)=0 so
+    c=f*0+i*0=0 and h=o*φ(0)=0 forever, for every LSTM cell activation
+    φ with φ(0)=0: tanh, relu and linear (relu'(0) is taken as 0 and
+    the pad units' dc, dh are 0 whatever φ' is). It FAILS for sigmoid:
+    σ(0)=0.5 makes pad units emit non-zero h, and the next layer's pad
+    rows then receive gradient; an LSTMPack with a sigmoid layer whose
+    dims would actually be padded therefore builds unpadded
+    (``LSTMPack._declare_params``). All the pad units' gradients are
     exactly 0 (dc=dh=0 chains), so every supported optimizer keeps
     their weights at 0 (each update is a multiple of g or of a moment
     of g). Every supported loss is 0 with zero gradient at d=0, so pad
@@ -780,11 +786,21 @@ class LSTMPack(BasePack):
 
     def _declare_params(self):
         spec = self.spec
+        lstm_layers = [l for l in spec.layers if l.kind == "lstm"]
+        # cell activation each layer runs, beside lstm_meta (a spec
+        # saved before the kernels took one runs tanh throughout)
+        self.lstm_acts = spec.lstm_activations()
+        if self.pad8 and "sigmoid" in self.lstm_acts and any(
+            n % 8 for n in [spec.n_features] + [l.units for l in lstm_layers]
+        ):
+            # sigmoid(0) != 0: pad units would not be inert (see
+            # pad_enabled), so this pack keeps its logical dims
+            self.pad8 = False
+            self._pad = lambda n: int(n)
         p = self._pad
         self.lstm_meta = []          # PHYSICAL (fin, H, return_sequences)
         self.lstm_meta_logical = []  # logical dims for serialization
         fin_l = spec.n_features
-        lstm_layers = [l for l in spec.layers if l.kind == "lstm"]
         dense_layers = [l for l in spec.layers if l.kind == "dense"]
         assert len(dense_layers) == 1, "LSTM spec needs exactly one output dense layer"
         self._logical_in = fin_l
@@ -864,6 +880,14 @@ class LSTMPack(BasePack):
             ops.lstm_seq_available(H) for _fin, H, _rs in self.lstm_meta
         ):
             return False
+        # only the v4 forward / pipelined backward kernels take a cell
+        # activation; otherwise the whole stack runs per timestep
+        # through the activation-aware pointwise kernels
+        if not all(
+            act == "tanh" or ops.lstm_act_scan_available(H, fin)
+            for (fin, H, _rs), act in zip(self.lstm_meta, self.lstm_acts)
+        ):
+            return False
         if any(H > 64 for _fin, H, _rs in self.lstm_meta):
             rows = B if B is not None else 256
             if self.G * ((rows + 31) // 32) < 256:
@@ -905,7 +929,9 @@ class LSTMPack(BasePack):
             for t in range(T):
                 gates = gates_all[:, :, t].contiguous()
                 ops.grouped_gemm_acc(h, Wh, gates)
-                h, c, gact = ops.lstm_pointwise_fwd(gates, c)
+                h, c, gact = ops.lstm_pointwise_fwd(
+                    gates, c, self.lstm_acts[li]
+                )
                 hs[:, :, t] = h
                 if keep:
                     cs[:, :, t] = c
@@ -939,13 +965,18 @@ class LSTMPack(BasePack):
             Wx = self.store.cviews[f"Wx{li}"]
             Wh = self.store.cviews[f"Wh{li}"]
             b = self.store.views[f"bl{li}"]
+            act = self.lstm_acts[li]
             if v4_on and ops.lstm_v4_available(H, fin):
                 out = ops.lstm_seq_fwd_fused(seq, Wx, Wh, b,
-                                             store_aux=keep)
+                                             store_aux=keep, act=act)
                 hs = out[0]
                 cs = out[1] if keep else None
                 gacts = out[2] if keep else None
             else:
+                if act != "tanh":  # _use_fused keeps such stacks out
+                    raise RuntimeError(
+                        f"no fused forward scan for LSTM activation {act!r}"
+                    )
                 xW = ops.grouped_linear_fwd(
                     seq.reshape(G, B * T, fin), Wx, b, "linear"
                 ).view(G, B, T, 4 * H)
@@ -1011,6 +1042,7 @@ class LSTMPack(BasePack):
                 dG_flat, next_dSeq = ops.lstm_seq_bwd_fused(
                     dh_last if last_only else dSeq,
                     lc["gacts"], lc["cs"], Wh, Wx, last_only,
+                    act=self.lstm_acts[li],
                 )
                 dG_flat = dG_flat.view(G, B * T, 4 * H)
             else:
@@ -1018,6 +1050,7 @@ class LSTMPack(BasePack):
                 dG_flat = ops.lstm_seq_bwd(
                     dh_last if last_only else dSeq,
                     lc["gacts"], lc["cs"], Wh, last_only,
+                    act=self.lstm_acts[li],
                 ).view(G, B * T, 4 * H)
             hs = lc["hs"]
             # combined pass: dZ (dG) staged once for both weight grads;
@@ -1091,7 +1124,8 @@ class LSTMPack(BasePack):
                     else torch.zeros_like(dc_carry)
                 )
                 dgates, dc_carry = ops.lstm_pointwise_bwd(
-                    dh_t, dc_carry, gacts[:, :, t], cs[:, :, t], c_prev
+                    dh_t, dc_carry, gacts[:, :, t], cs[:, :, t], c_prev,
+                    self.lstm_acts[li],
                 )
                 dG[:, :, t] = dgates
                 dh_carry = ops.grouped_linear_bwd_data(dgates, Wh)

@@ -8,8 +8,11 @@ lstm_autoencoder.py) produce these specs; the packed engine
 """
 from __future__ import annotations
 
+import logging
 from dataclasses import dataclass, field, asdict
 from typing import Any, Dict, List, Optional, Tuple
+
+logger = logging.getLogger(__name__)
 
 
 # ---- compile settings -------------------------------------------------
@@ -42,6 +45,29 @@ _OPTIMIZER_DEFAULTS: Dict[str, Dict[str, Any]] = {
     "adamax": dict(learning_rate=0.001, beta_1=0.9, beta_2=0.999,
                    epsilon=1e-7),
 }
+
+
+# cell activations the LSTM kernels implement (the candidate gate and
+# φ(c); the i/f/o gates are always sigmoid). Same rule as above: any
+# other name raises instead of silently training tanh.
+LSTM_ACTIVATIONS = ("linear", "relu", "sigmoid", "tanh")
+
+
+def normalize_lstm_activation(name: Any) -> str:
+    """Canonical LSTM cell activation; ``None`` is linear, as for Dense.
+
+    >>> normalize_lstm_activation("ReLU"), normalize_lstm_activation(None)
+    ('relu', 'linear')
+    """
+    key = "linear" if name is None else (
+        name.lower() if isinstance(name, str) else None
+    )
+    if key not in LSTM_ACTIVATIONS:
+        raise ValueError(
+            f"Unsupported LSTM activation {name!r}; supported: "
+            f"{sorted(LSTM_ACTIVATIONS)}"
+        )
+    return key
 
 
 def _is_off(v: Any) -> bool:
@@ -209,6 +235,10 @@ class ModelSpec:
     optimizer: str = "Adam"
     optimizer_kwargs: Dict[str, Any] = field(default_factory=dict)
     loss_kwargs: Dict[str, Any] = field(default_factory=dict)
+    # 1: LSTM layers run their configured activation. 0 (specs saved
+    # before the kernels took one): every LSTM layer was trained as
+    # tanh whatever its stored name says, and keeps running tanh.
+    lstm_act_version: int = 1
 
     def __post_init__(self):
         # unsupported compile settings fail HERE, when the spec is
@@ -218,17 +248,29 @@ class ModelSpec:
         self.loss_kwargs = dict(self.loss_kwargs or {})
         resolve_loss(self.loss, self.loss_kwargs)
         resolve_optimizer(self.optimizer, self.optimizer_kwargs)
+        for layer in self.layers:
+            if layer.kind == "lstm":
+                normalize_lstm_activation(layer.activation)
 
     def __setstate__(self, state):
         # specs pickled inside estimators saved before ``loss_kwargs``
-        # existed restore without it (unpickling bypasses __init__)
+        # / ``lstm_act_version`` existed restore without them
+        # (unpickling bypasses __init__)
         self.__dict__.update(state)
         self.__dict__.setdefault("loss_kwargs", {})
+        self.__dict__.setdefault("lstm_act_version", 0)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_lstm_act_warned", None)
+        return state
 
     def to_dict(self) -> Dict[str, Any]:
         d = asdict(self)
         if not d["loss_kwargs"]:
             del d["loss_kwargs"]
+        if d["lstm_act_version"] == 1:
+            del d["lstm_act_version"]
         return d
 
     @classmethod
@@ -248,6 +290,27 @@ class ModelSpec:
             prev = layer.units
         return dims
 
+    def lstm_activations(self) -> List[str]:
+        """Canonical cell activation each LSTM layer RUNS, in layer
+        order. A version-0 spec runs tanh throughout; the first call
+        logs one warning if a stored name says otherwise."""
+        names = [
+            normalize_lstm_activation(l.activation)
+            for l in self.layers if l.kind == "lstm"
+        ]
+        if self.lstm_act_version >= 1:
+            return names
+        stale = sorted({n for n in names if n != "tanh"})
+        if stale and not self.__dict__.get("_lstm_act_warned"):
+            self.__dict__["_lstm_act_warned"] = True
+            logger.warning(
+                "This model was saved when LSTM layers ignored their "
+                "configured activation (%s): it was trained as tanh and "
+                "keeps running tanh. Rebuild it to train the configured "
+                "activation.", ", ".join(stale),
+            )
+        return ["tanh"] * len(names)
+
     def arch_key(self) -> tuple:
         """Hashable architecture key — models with equal keys can share
         one pack (grouped-GEMM batch)."""
@@ -261,6 +324,7 @@ class ModelSpec:
             ),
             self.lookback_window,
             self.lookahead,
+            self.lstm_act_version,
             # normalised, defaults filled in: "adam"/"Adam" and
             # "mse"/"mean_squared_error" share a pack
             self.loss_kind,

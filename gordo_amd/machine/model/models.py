@@ -474,10 +474,18 @@ def _parse_raw_spec(
             )
         elif lname == "LSTM":
             has_lstm = True
+            rec_act = lkw.get("recurrent_activation", "sigmoid")
+            if not (isinstance(rec_act, str) and rec_act.lower() == "sigmoid"):
+                raise ValueError(
+                    f"Unsupported LSTM recurrent_activation {rec_act!r}: "
+                    "the engine's gates are sigmoid"
+                )
             layers.append(
                 LayerSpec(
                     kind="lstm",
                     units=int(lkw.get("units", n_features_out)),
+                    # Keras' LSTM default; None is linear, as in Keras
+                    activation=lkw.get("activation", "tanh"),
                     return_sequences=bool(lkw.get("return_sequences", False)),
                 )
             )

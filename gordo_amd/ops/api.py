@@ -263,15 +263,32 @@ def lstm_v4_available(H: int, F: int) -> bool:
         and F <= 128
 
 
-def lstm_seq_fwd_fused(xseq, Wx, Wh, bias, store_aux=True):
+def lstm_act_scan_available(H: int, F: int) -> bool:
+    """Whether the fused scans serve a non-tanh cell activation at
+    this geometry. Only the v4 forward and the pipelined backward
+    kernel take one, so both must apply: the v4 geometry with F >= 8
+    and neither ``GORDO_LSTM_V4=0`` nor ``GORDO_LSTM_PIPE=0`` set."""
+    import os as _os
+
+    return (
+        lstm_v4_available(H, F)
+        and F >= 8
+        and _os.environ.get("GORDO_LSTM_V4", "1") != "0"
+        and _os.environ.get("GORDO_LSTM_PIPE", "1") != "0"
+    )
+
+
+def lstm_seq_fwd_fused(xseq, Wx, Wh, bias, store_aux=True, act="tanh"):
     """v4 scan: the x-side gate GEMM runs INSIDE the recurrence over an
     LDS-resident [Wh ; Wx] tile — no xW round trip through HBM (the
     fleet's scans are bandwidth-bound). ``store_aux=False`` skips the
     cs/gacts stores for inference. GORDO_LSTM_V4=0 falls back to the
-    two-step path at the engine level."""
+    two-step path at the engine level. ``act`` is the cell activation
+    (tanh/relu/sigmoid/linear) of the candidate gate and of φ(c)."""
+    act = act_code(act)
     if _on_gpu(xseq):
         return _require_hip().lstm_seq_fwd_fused(
-            xseq, Wx, Wh, bias, bool(store_aux)
+            xseq, Wx, Wh, bias, bool(store_aux), act
         )
     # CPU oracle: explicit xW then the per-timestep reference scan
     G, B, T, F = xseq.shape
@@ -286,7 +303,7 @@ def lstm_seq_fwd_fused(xseq, Wx, Wh, bias, store_aux=True):
     ga = torch.empty(G, B, T, 4 * H, dtype=xseq.dtype)
     for t in range(T):
         gates = gates_all[:, :, t] + torch.bmm(h, Wh)
-        h, c, gact = ref.lstm_pointwise_fwd(gates, c)
+        h, c, gact = ref.lstm_pointwise_fwd(gates, c, act)
         hs[:, :, t] = h
         cs[:, :, t] = c
         ga[:, :, t] = gact
@@ -335,14 +352,25 @@ def last_scan_launch() -> dict:
     }
 
 
-def lstm_seq_bwd(dSeq, gacts, cs, Wh, last_only):
+def last_scan_activation() -> str:
+    """Cell activation name of this thread's last scan launch (kept
+    beside ``last_scan_launch``): "tanh" for every tanh-only family."""
+    return _require_hip().last_scan_activation()
+
+
+def lstm_seq_bwd(dSeq, gacts, cs, Wh, last_only, act="tanh"):
     """Fused on-device LSTM backward (BPTT) scan (GPU only). Same
     version dispatch as ``lstm_seq_fwd``: pipelined v3 by default for
     the barriered layout, v2 for H%16==0, big-H kernels for H>64;
-    ``GORDO_LSTM_V1=1`` forces the unpipelined v1 scan."""
+    ``GORDO_LSTM_V1=1`` forces the unpipelined v1 scan. A non-tanh
+    ``act`` goes straight to the ``lstm_seq_bwd_v3`` entry: only the
+    pipelined kernel behind it takes a cell activation."""
     import os as _os
 
     ext = _require_hip()
+    act = act_code(act)
+    if act != ACT_TANH:
+        return ext.lstm_seq_bwd_v3(dSeq, gacts, cs, Wh, bool(last_only), act)
     G, B = gacts.shape[0], gacts.shape[1]
     H = gacts.shape[-1] // 4
     v2_fills = H % 16 == 0 and G * ((B + 63) // 64) >= 256
@@ -355,18 +383,44 @@ def lstm_seq_bwd(dSeq, gacts, cs, Wh, last_only):
     return ext.lstm_seq_bwd_v3(dSeq, gacts, cs, Wh, last_only)
 
 
-def lstm_seq_bwd_fused(dSeq, gacts, cs, Wh, Wx, last_only):
+def _lstm_seq_bwd_cpu(dSeq, gacts, cs, Wh, last_only, act):
+    """fp32 per-timestep BPTT over the pointwise reference (CPU lane)."""
+    G, B, T, H4 = gacts.shape
+    H = H4 // 4
+    WhT = Wh.transpose(1, 2)
+    dh_carry = torch.zeros(G, B, H, dtype=gacts.dtype)
+    dc = torch.zeros(G, B, H, dtype=cs.dtype)
+    dG = torch.empty_like(gacts)
+    zero_c = torch.zeros_like(cs[:, :, 0])
+    for t in range(T - 1, -1, -1):
+        dh = dh_carry
+        if not last_only:
+            dh = dh + dSeq[:, :, t]
+        elif t == T - 1:
+            dh = dh + dSeq
+        c_prev = cs[:, :, t - 1] if t > 0 else zero_c
+        dg, dc = ref.lstm_pointwise_bwd(
+            dh, dc, gacts[:, :, t], cs[:, :, t], c_prev, act
+        )
+        dG[:, :, t] = dg
+        dh_carry = torch.bmm(dg, WhT)
+    return dG
+
+
+def lstm_seq_bwd_fused(dSeq, gacts, cs, Wh, Wx, last_only, act="tanh"):
     """v5 reverse scan with the bwd-data GEMM fused in: returns
     (dG, dX) where dX = dG @ Wx^T computed per step against an
     LDS-resident WxT (no dG HBM re-read). Geometry: H<=64, F<=128.
     H%8==0 and F%8==0 take the 16-byte pipelined kernel (bit-identical
-    outputs); ``GORDO_LSTM_PIPE=0`` forces the v5 kernel."""
+    outputs); ``GORDO_LSTM_PIPE=0`` forces the v5 kernel. A non-tanh
+    ``act`` runs only on the pipelined kernel and raises elsewhere."""
+    act = act_code(act)
     if _on_gpu(gacts):
         out = _require_hip().lstm_seq_bwd_fused(
-            dSeq, gacts, cs, Wh, Wx, bool(last_only)
+            dSeq, gacts, cs, Wh, Wx, bool(last_only), act
         )
         return out[0], out[1]
-    dG = lstm_seq_bwd(dSeq, gacts, cs, Wh, last_only)
+    dG = _lstm_seq_bwd_cpu(dSeq, gacts, cs, Wh, last_only, act)
     G, B, T, H4 = gacts.shape
     dX = ref.grouped_linear_bwd_data(
         dG.view(G, B * T, H4), Wx
@@ -374,27 +428,34 @@ def lstm_seq_bwd_fused(dSeq, gacts, cs, Wh, Wx, last_only):
     return dG, dX
 
 
-def lstm_seq_bwd_v3(dSeq, gacts, cs, Wh, last_only):
+def lstm_seq_bwd_v3(dSeq, gacts, cs, Wh, last_only, act="tanh"):
     """The bottom-layer backward scan, directly (for A/B tests): the
     16-byte pipelined kernel when H % 8 == 0, else the v3 kernel;
-    ``GORDO_LSTM_PIPE=0`` forces v3."""
-    return _require_hip().lstm_seq_bwd_v3(dSeq, gacts, cs, Wh, last_only)
+    ``GORDO_LSTM_PIPE=0`` forces v3. A non-tanh ``act`` runs only on
+    the pipelined kernel and raises elsewhere."""
+    act = act_code(act)
+    if not _on_gpu(gacts):
+        return _lstm_seq_bwd_cpu(dSeq, gacts, cs, Wh, last_only, act)
+    return _require_hip().lstm_seq_bwd_v3(
+        dSeq, gacts, cs, Wh, bool(last_only), act
+    )
 
 
-def lstm_seq_bwd_fused_out(dSeq, gacts, cs, Wh, Wx, last_only, dG, dX):
+def lstm_seq_bwd_fused_out(dSeq, gacts, cs, Wh, Wx, last_only, dG, dX,
+                           act="tanh"):
     """``lstm_seq_bwd_fused`` (GPU only) writing into caller-provided
     contiguous, 16-byte-aligned bf16 ``dG`` [G,B,T,4H] and ``dX``
     [G,B,T,F] — lets tests place the outputs between guard regions."""
     _require_hip().lstm_seq_bwd_fused_out(
-        dSeq, gacts, cs, Wh, Wx, bool(last_only), dG, dX
+        dSeq, gacts, cs, Wh, Wx, bool(last_only), dG, dX, act_code(act)
     )
 
 
-def lstm_seq_bwd_v3_out(dSeq, gacts, cs, Wh, last_only, dG):
+def lstm_seq_bwd_v3_out(dSeq, gacts, cs, Wh, last_only, dG, act="tanh"):
     """``lstm_seq_bwd_v3`` (GPU only, H <= 64) into a caller-provided
     ``dG`` (same contract as ``lstm_seq_bwd_fused_out``)."""
     _require_hip().lstm_seq_bwd_v3_out(
-        dSeq, gacts, cs, Wh, bool(last_only), dG
+        dSeq, gacts, cs, Wh, bool(last_only), dG, act_code(act)
     )
 
 
@@ -455,13 +516,17 @@ def row_quantile(X, q: float):
     )
 
 
-def lstm_pointwise_fwd(gates, c_prev):
+def lstm_pointwise_fwd(gates, c_prev, act="tanh"):
+    act = act_code(act)
     if _on_gpu(gates):
-        return _require_hip().lstm_pointwise_fwd(gates, c_prev)
-    return ref.lstm_pointwise_fwd(gates, c_prev)
+        return _require_hip().lstm_pointwise_fwd(gates, c_prev, act)
+    return ref.lstm_pointwise_fwd(gates, c_prev, act)
 
 
-def lstm_pointwise_bwd(dh, dc_next, gact, c, c_prev):
+def lstm_pointwise_bwd(dh, dc_next, gact, c, c_prev, act="tanh"):
+    act = act_code(act)
     if _on_gpu(dh):
-        return _require_hip().lstm_pointwise_bwd(dh, dc_next, gact, c, c_prev)
-    return ref.lstm_pointwise_bwd(dh, dc_next, gact, c, c_prev)
+        return _require_hip().lstm_pointwise_bwd(
+            dh, dc_next, gact, c, c_prev, act
+        )
+    return ref.lstm_pointwise_bwd(dh, dc_next, gact, c, c_prev, act)

@@ -490,8 +490,28 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
   }
 }
 
+// LSTM cell activation φ (candidate gate and φ(c)) by act code, a
+// compile-time parameter of the pointwise kernels; relu and linear
+// evaluate no exponential.
+template <int ACT>
+DEV_INLINE float cell_act(float x) {
+  if constexpr (ACT == ACT_TANH) return fast_tanhf(x);
+  else if constexpr (ACT == ACT_SIGMOID) return 1.f / (1.f + __expf(-x));
+  else if constexpr (ACT == ACT_RELU) return fmaxf(x, 0.f);
+  else return x;
+}
+// φ'(z) from the stored output y = φ(z)
+template <int ACT>
+DEV_INLINE float cell_dact(float y) {
+  if constexpr (ACT == ACT_TANH) return 1.f - y * y;
+  else if constexpr (ACT == ACT_SIGMOID) return y * (1.f - y);
+  else if constexpr (ACT == ACT_RELU) return y > 0.f ? 1.f : 0.f;
+  else return 1.f;
+}
+
 // LSTM pointwise fwd: gates[g,b,4H] pre-act (+c_prev f32) ->
 // h bf16, c f32, gact bf16 (keras gate order i,f,g,o).
+template <int ACT>
 __global__ void lstm_pw_fwd_kernel(const bf16* __restrict__ gates,
                                    const float* __restrict__ c_prev,
                                    bf16* __restrict__ h, float* __restrict__ c,
@@ -506,11 +526,11 @@ __global__ void lstm_pw_fwd_kernel(const bf16* __restrict__ gates,
     const bf16* grow = gates + row * 4 * H;
     float i_g = 1.f / (1.f + __expf(-bf2f(grow[hh])));
     float f_g = 1.f / (1.f + __expf(-bf2f(grow[H + hh])));
-    float g_g = fast_tanhf(bf2f(grow[2 * H + hh]));
+    float g_g = cell_act<ACT>(bf2f(grow[2 * H + hh]));
     float o_g = 1.f / (1.f + __expf(-bf2f(grow[3 * H + hh])));
     float cc = f_g * c_prev[idx] + i_g * g_g;
     c[idx] = cc;
-    h[idx] = f2bf(o_g * fast_tanhf(cc));
+    h[idx] = f2bf(o_g * cell_act<ACT>(cc));
     bf16* ga = gact + row * 4 * H;
     ga[hh] = f2bf(i_g);
     ga[H + hh] = f2bf(f_g);
@@ -520,6 +540,7 @@ __global__ void lstm_pw_fwd_kernel(const bf16* __restrict__ gates,
 }
 
 // LSTM pointwise bwd -> dgates (pre-act) bf16, dc_prev f32
+template <int ACT>
 __global__ void lstm_pw_bwd_kernel(
     const bf16* __restrict__ dh, const float* __restrict__ dc_next,
     const bf16* __restrict__ gact, const float* __restrict__ c,
@@ -536,9 +557,9 @@ __global__ void lstm_pw_bwd_kernel(
     float f_g = bf2f(ga[H + hh]);
     float g_g = bf2f(ga[2 * H + hh]);
     float o_g = bf2f(ga[3 * H + hh]);
-    float tc = fast_tanhf(c[idx]);
+    float tc = cell_act<ACT>(c[idx]);
     float dhv = bf2f(dh[idx]);
-    float dc = dc_next[idx] + dhv * o_g * (1.f - tc * tc);
+    float dc = dc_next[idx] + dhv * o_g * cell_dact<ACT>(tc);
     float di = dc * g_g;
     float df = dc * c_prev[idx];
     float dg = dc * i_g;
@@ -547,7 +568,7 @@ __global__ void lstm_pw_bwd_kernel(
     bf16* dgrow = dgates + row * 4 * H;
     dgrow[hh] = f2bf(di * i_g * (1.f - i_g));
     dgrow[H + hh] = f2bf(df * f_g * (1.f - f_g));
-    dgrow[2 * H + hh] = f2bf(dg * (1.f - g_g * g_g));
+    dgrow[2 * H + hh] = f2bf(dg * cell_dact<ACT>(g_g));
     dgrow[3 * H + hh] = f2bf(do_ * o_g * (1.f - o_g));
   }
 }
@@ -859,9 +880,27 @@ void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                      step_buf.data_ptr<int>());
 }
 
+// launch K<ACT>(args...) for the cell activation code `act`
+#define GORDO_CELL_ACT_LAUNCH(K, ...)                                       \
+  do {                                                                      \
+    switch (act) {                                                          \
+      case ACT_LINEAR:                                                      \
+        hipLaunchKernelGGL(K<ACT_LINEAR>, __VA_ARGS__); break;              \
+      case ACT_RELU:                                                        \
+        hipLaunchKernelGGL(K<ACT_RELU>, __VA_ARGS__); break;                \
+      case ACT_SIGMOID:                                                     \
+        hipLaunchKernelGGL(K<ACT_SIGMOID>, __VA_ARGS__); break;             \
+      default:                                                              \
+        hipLaunchKernelGGL(K<ACT_TANH>, __VA_ARGS__); break;                \
+    }                                                                       \
+  } while (0)
+
 std::vector<torch::Tensor> lstm_pointwise_fwd(torch::Tensor gates,
-                                              torch::Tensor c_prev) {
+                                              torch::Tensor c_prev,
+                                              int64_t act) {
   CHECK_GPU(gates);
+  TORCH_CHECK(act >= ACT_LINEAR && act <= ACT_SIGMOID,
+              "unknown LSTM cell activation code ", act);
   auto gc = to_bf16c(gates);
   auto cp = c_prev.to(torch::kFloat32).contiguous();
   int H4 = gc.size(-1);
@@ -874,10 +913,10 @@ std::vector<torch::Tensor> lstm_pointwise_fwd(torch::Tensor gates,
   auto gact = torch::empty_like(gc);
   size_t n = rows * H;
   int blocks = (int)std::min<size_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(lstm_pw_fwd_kernel, dim3(blocks), dim3(256), 0,
-                     cur_stream(), (const bf16*)gc.data_ptr(),
-                     cp.data_ptr<float>(), (bf16*)h.data_ptr(),
-                     c.data_ptr<float>(), (bf16*)gact.data_ptr(), rows, H);
+  GORDO_CELL_ACT_LAUNCH(lstm_pw_fwd_kernel, dim3(blocks), dim3(256), 0,
+                        cur_stream(), (const bf16*)gc.data_ptr(),
+                        cp.data_ptr<float>(), (bf16*)h.data_ptr(),
+                        c.data_ptr<float>(), (bf16*)gact.data_ptr(), rows, H);
   return {h, c, gact};
 }
 
@@ -885,8 +924,11 @@ std::vector<torch::Tensor> lstm_pointwise_bwd(torch::Tensor dh,
                                               torch::Tensor dc_next,
                                               torch::Tensor gact,
                                               torch::Tensor c,
-                                              torch::Tensor c_prev) {
+                                              torch::Tensor c_prev,
+                                              int64_t act) {
   CHECK_GPU(dh);
+  TORCH_CHECK(act >= ACT_LINEAR && act <= ACT_SIGMOID,
+              "unknown LSTM cell activation code ", act);
   auto dhc = to_bf16c(dh);
   auto dcn = dc_next.to(torch::kFloat32).contiguous();
   auto gc = to_bf16c(gact);
@@ -898,14 +940,15 @@ std::vector<torch::Tensor> lstm_pointwise_bwd(torch::Tensor dh,
   auto dc_prev = torch::empty_like(cc);
   size_t n = rows * H;
   int blocks = (int)std::min<size_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(lstm_pw_bwd_kernel, dim3(blocks), dim3(256), 0,
-                     cur_stream(), (const bf16*)dhc.data_ptr(),
-                     dcn.data_ptr<float>(), (const bf16*)gc.data_ptr(),
-                     cc.data_ptr<float>(), cpc.data_ptr<float>(),
-                     (bf16*)dgates.data_ptr(), dc_prev.data_ptr<float>(),
-                     rows, H);
+  GORDO_CELL_ACT_LAUNCH(lstm_pw_bwd_kernel, dim3(blocks), dim3(256), 0,
+                        cur_stream(), (const bf16*)dhc.data_ptr(),
+                        dcn.data_ptr<float>(), (const bf16*)gc.data_ptr(),
+                        cc.data_ptr<float>(), cpc.data_ptr<float>(),
+                        (bf16*)dgates.data_ptr(), dc_prev.data_ptr<float>(),
+                        rows, H);
   return {dgates, dc_prev};
 }
+#undef GORDO_CELL_ACT_LAUNCH
 
 }  // namespace
 
@@ -924,25 +967,26 @@ std::vector<torch::Tensor> lstm_seq_fwd_fused(torch::Tensor xseq,
                                               torch::Tensor Wx,
                                               torch::Tensor Wh,
                                               torch::Tensor bias,
-                                              bool store_aux);
+                                              bool store_aux, int64_t act);
 std::vector<torch::Tensor> lstm_seq_fwd_v3(torch::Tensor xW, torch::Tensor Wh);
 torch::Tensor lstm_seq_bwd_v3(torch::Tensor dSeq, torch::Tensor gacts,
                               torch::Tensor cs, torch::Tensor Wh,
-                              bool last_only);
+                              bool last_only, int64_t act);
 std::vector<torch::Tensor> lstm_seq_bwd_fused(
     torch::Tensor dSeq, torch::Tensor gacts, torch::Tensor cs,
-    torch::Tensor Wh, torch::Tensor Wx, bool last_only);
+    torch::Tensor Wh, torch::Tensor Wx, bool last_only, int64_t act);
 torch::Tensor lstm_seq_bwd(torch::Tensor dSeq, torch::Tensor gacts,
                            torch::Tensor cs, torch::Tensor Wh,
                            bool last_only);
 void lstm_seq_bwd_fused_out(torch::Tensor dSeq, torch::Tensor gacts,
                             torch::Tensor cs, torch::Tensor Wh,
                             torch::Tensor Wx, bool last_only,
-                            torch::Tensor dG, torch::Tensor dX);
+                            torch::Tensor dG, torch::Tensor dX, int64_t act);
 void lstm_seq_bwd_v3_out(torch::Tensor dSeq, torch::Tensor gacts,
                          torch::Tensor cs, torch::Tensor Wh, bool last_only,
-                         torch::Tensor dG);
+                         torch::Tensor dG, int64_t act);
 std::tuple<std::string, int, int, int, int> last_scan_launch();
+std::string last_scan_activation();
 }  // namespace gordo_lstm
 
 // device threshold/statistics kernels (thresholds.hip: K10-K12)
@@ -982,25 +1026,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "NaN-dropping linear-interpolated quantile per row (K12)");
   mod.def("anomaly_score", &gordo_anomaly::anomaly_score,
           "fused DiffBased anomaly scoring (serving hot path)");
-  mod.def("lstm_seq_bwd_v3", &gordo_lstm::lstm_seq_bwd_v3,
+  // trailing `act`: the LSTM cell activation code, tanh by default
+  mod.def("lstm_seq_bwd_v3", &gordo_lstm::lstm_seq_bwd_v3, py::arg("dSeq"),
+          py::arg("gacts"), py::arg("cs"), py::arg("Wh"),
+          py::arg("last_only"), py::arg("act") = (int64_t)ACT_TANH,
           "pipelined fused LSTM backward scan (GORDO_LSTM_V3 opt-in)");
   mod.def("lstm_seq_fwd_v3", &gordo_lstm::lstm_seq_fwd_v3,
           "pipelined fused LSTM forward scan (GORDO_LSTM_V3 opt-in)");
   mod.def("lstm_seq_fwd", &gordo_lstm::lstm_seq_fwd,
           "fused LSTM forward sequence scan (Wh resident in LDS)");
   mod.def("lstm_seq_fwd_fused", &gordo_lstm::lstm_seq_fwd_fused,
+          py::arg("xseq"), py::arg("Wx"), py::arg("Wh"), py::arg("bias"),
+          py::arg("store_aux"), py::arg("act") = (int64_t)ACT_TANH,
           "v4 scan with the x-side gate GEMM fused in (halves fwd "
           "HBM traffic); store_aux=false skips cs/gacts (inference)");
   mod.def("lstm_seq_bwd", &gordo_lstm::lstm_seq_bwd,
           "fused LSTM backward (BPTT) sequence scan");
   mod.def("lstm_seq_bwd_fused", &gordo_lstm::lstm_seq_bwd_fused,
+          py::arg("dSeq"), py::arg("gacts"), py::arg("cs"), py::arg("Wh"),
+          py::arg("Wx"), py::arg("last_only"),
+          py::arg("act") = (int64_t)ACT_TANH,
           "v5 reverse scan with dSeq = dG@Wx^T fused in");
   mod.def("lstm_seq_bwd_fused_out", &gordo_lstm::lstm_seq_bwd_fused_out,
+          py::arg("dSeq"), py::arg("gacts"), py::arg("cs"), py::arg("Wh"),
+          py::arg("Wx"), py::arg("last_only"), py::arg("dG"), py::arg("dX"),
+          py::arg("act") = (int64_t)ACT_TANH,
           "lstm_seq_bwd_fused into caller-provided dG, dX");
+  mod.def("last_scan_activation", &gordo_lstm::last_scan_activation,
+          "cell activation name of this thread's last scan-kernel launch");
   mod.def("last_scan_launch", &gordo_lstm::last_scan_launch,
           "(family, rows, hf, has_dx, last_only) of this thread's last "
           "scan-kernel launch");
   mod.def("lstm_seq_bwd_v3_out", &gordo_lstm::lstm_seq_bwd_v3_out,
+          py::arg("dSeq"), py::arg("gacts"), py::arg("cs"), py::arg("Wh"),
+          py::arg("last_only"), py::arg("dG"),
+          py::arg("act") = (int64_t)ACT_TANH,
           "lstm_seq_bwd_v3 into a caller-provided dG");
   mod.def("grouped_linear_fwd", &grouped_linear_fwd,
           "Y = act(X@W + b) per group (MFMA)");
@@ -1024,6 +1084,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "fused per-model MSE loss + grad (real_n: divisor when the "
           "feature dim is zero-padded)");
   mod.def("adam_step", &adam_step, "fused Adam + bf16 mirror refresh");
-  mod.def("lstm_pointwise_fwd", &lstm_pointwise_fwd, "LSTM cell fwd");
-  mod.def("lstm_pointwise_bwd", &lstm_pointwise_bwd, "LSTM cell bwd");
+  mod.def("lstm_pointwise_fwd", &lstm_pointwise_fwd, py::arg("gates"),
+          py::arg("c_prev"), py::arg("act") = (int64_t)ACT_TANH,
+          "LSTM cell fwd");
+  mod.def("lstm_pointwise_bwd", &lstm_pointwise_bwd, py::arg("dh"),
+          py::arg("dc_next"), py::arg("gact"), py::arg("c"),
+          py::arg("c_prev"), py::arg("act") = (int64_t)ACT_TANH,
+          "LSTM cell bwd");
 }

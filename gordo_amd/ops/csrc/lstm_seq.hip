@@ -27,6 +27,7 @@
 
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #define DEV_INLINE __device__ __forceinline__
@@ -48,6 +49,40 @@ DEV_INLINE float fast_tanhf_(float x) {
   float e = __expf(2.f * x);
   return 1.f - 2.f / (e + 1.f);  // saturates to 1 when e overflows to inf
 }
+
+// Cell activation φ of the candidate gate and of φ(c), by the codes of
+// ops/reference.py act_code. A compile-time parameter of the v4
+// forward and the pipelined backward scan: only the gate phase differs
+// between instantiations, and relu / linear evaluate no exponential.
+constexpr int CELL_LINEAR = 0, CELL_TANH = 1, CELL_RELU = 2,
+              CELL_SIGMOID = 3;
+template <int ACT>
+DEV_INLINE float cell_act_(float x) {
+  if constexpr (ACT == CELL_TANH) return fast_tanhf_(x);
+  else if constexpr (ACT == CELL_SIGMOID) return sigmoidf_(x);
+  else if constexpr (ACT == CELL_RELU) return fmaxf(x, 0.f);
+  else return x;
+}
+// φ'(z) from the stored output y = φ(z) (relu: y > 0 <=> z > 0)
+template <int ACT>
+DEV_INLINE float cell_dact_(float y) {
+  if constexpr (ACT == CELL_TANH) return 1.f - y * y;
+  else if constexpr (ACT == CELL_SIGMOID) return y * (1.f - y);
+  else if constexpr (ACT == CELL_RELU) return y > 0.f ? 1.f : 0.f;
+  else return 1.f;
+}
+
+// Element type of the v4 forward's pre-activation tile gS (MFMA
+// epilogue -> gate phase). tanh keeps the bf16 tile it has always had.
+// The other activations keep fp32: relu and linear do not damp the
+// bf16 rounding of z_g (2^-9 |z_g|) the way tanh's slope does, it would
+// enter c whole at every step, and c is the fp32 state of the cell.
+template <int ACT>
+using gate_tile_t = std::conditional_t<ACT == CELL_TANH, bf16, float>;
+DEV_INLINE void put_gate(bf16* p, float v) { *p = lf2bf(v); }
+DEV_INLINE void put_gate(float* p, float v) { *p = v; }
+DEV_INLINE float get_gate(const bf16* p) { return lbf2f(*p); }
+DEV_INLINE float get_gate(const float* p) { return *p; }
 
 constexpr int LDK = 72;    // padded K-row length for h / WhT tiles (bf16)
 // ROWS (window rows per workgroup) is a template parameter: 64 rows for
@@ -746,11 +781,12 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_v3_kernel(
 //     stores. In program order the prefetch loads precede the step's
 //     stores, so the counted wait on the loads leaves the stores in
 //     flight.
-// HAS_DX=false is the bottom-layer scan (no Wx, no dX).
+// HAS_DX=false is the bottom-layer scan (no Wx, no dX). ACT is the cell
+// activation (gate phase only).
 // ===========================================================================
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
-template <int ROWS, bool HAS_DX, bool LAST_ONLY>
+template <int ROWS, bool HAS_DX, bool LAST_ONLY, int ACT>
 __global__ __launch_bounds__(256) void lstm_seq_bwd_pipe_kernel(
     const bf16* __restrict__ dSeq, const bf16* __restrict__ gacts,
     const float* __restrict__ cs, const bf16* __restrict__ Wh,
@@ -898,8 +934,8 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_pipe_kernel(
       float dh = lbf2f(dhS[row * LDK + hh]);
       if (!LAST_ONLY)
         dh += lbf2f(reinterpret_cast<const bf16*>(rp + 12 * H)[hh]);
-      float tc = fast_tanhf_(cc);
-      float dc = dcS[row * H + hh] + dh * o_g * (1.f - tc * tc);
+      float tc = cell_act_<ACT>(cc);
+      float dc = dcS[row * H + hh] + dh * o_g * cell_dact_<ACT>(tc);
       float di = dc * g_g;
       float df = dc * cp;
       float dg = dc * i_g;
@@ -907,7 +943,7 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_pipe_kernel(
       dcS[row * H + hh] = dc * f_g;
       float vi = di * i_g * (1.f - i_g);
       float vf = df * f_g * (1.f - f_g);
-      float vg = dg * (1.f - g_g * g_g);
+      float vg = dg * cell_dact_<ACT>(g_g);
       float vo = do_ * o_g * (1.f - o_g);
       dgS[row * ldg + hh] = lf2bf(vi);
       dgS[row * ldg + H + hh] = lf2bf(vf);
@@ -1618,8 +1654,10 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_big_kernel(
 // STORE_AUX=false additionally skips the cs/gacts stores for
 // inference (predict/CV-validation passes need only hs).
 // Geometry: H <= 64, H % 8 == 0, F % 8 == 0 (the pad8 engine layout).
+// ACT is the cell activation: it selects φ in the gate phase and the
+// element type of gS (gate_tile_t: bf16 for tanh, fp32 otherwise).
 // ===========================================================================
-template <int ROWS, bool STORE_AUX>
+template <int ROWS, bool STORE_AUX, int ACT>
 __global__ __launch_bounds__(256) void lstm_seq_fwd_v4_kernel(
     const bf16* __restrict__ xseq,   // [G, B, T, F]
     const bf16* __restrict__ WcatT,  // [G, 4H, Kc] (Kc = H + F)
@@ -1634,8 +1672,10 @@ __global__ __launch_bounds__(256) void lstm_seq_fwd_v4_kernel(
   const int LDKc = ((Kc + 31) & ~31) + 8;
   bf16* WT = reinterpret_cast<bf16*>(smem);               // [H4][LDKc]
   bf16* hxS = WT + (size_t)H4 * LDKc;                     // [ROWS][LDKc]
-  bf16* gS = hxS + (size_t)ROWS * LDKc;                   // [ROWS][ldg]
-  bf16* bS = gS + (size_t)ROWS * ldg;                     // [ldg]
+  using gate_t = gate_tile_t<ACT>;
+  gate_t* gS = reinterpret_cast<gate_t*>(hxS + (size_t)ROWS * LDKc);
+                                                          // [ROWS][ldg]
+  bf16* bS = reinterpret_cast<bf16*>(gS + (size_t)ROWS * ldg);  // [ldg]
   float* cS = reinterpret_cast<float*>(bS + ldg);         // [ROWS][H]
 
   const int nb = (B + ROWS - 1) / ROWS;
@@ -1718,7 +1758,7 @@ __global__ __launch_bounds__(256) void lstm_seq_fwd_v4_kernel(
           #pragma unroll
           for (int r = 0; r < 4; ++r) {
             int row = fm * 16 + kslot * 4 + r;
-            gS[row * ldg + col] = lf2bf(acc[fm][fn][r] + bv);
+            put_gate(&gS[row * ldg + col], acc[fm][fn][r] + bv);
           }
         }
       }
@@ -1745,13 +1785,13 @@ __global__ __launch_bounds__(256) void lstm_seq_fwd_v4_kernel(
     // ---- fused gate math + h/c update + outputs ----
     for (int e = tid; e < ROWS * H; e += 256) {
       int row = e / H, hh = e % H;
-      const bf16* grow = &gS[row * ldg];
-      float i_g = sigmoidf_(lbf2f(grow[hh]));
-      float f_g = sigmoidf_(lbf2f(grow[H + hh]));
-      float g_g = fast_tanhf_(lbf2f(grow[2 * H + hh]));
-      float o_g = sigmoidf_(lbf2f(grow[3 * H + hh]));
+      const gate_t* grow = &gS[row * ldg];
+      float i_g = sigmoidf_(get_gate(&grow[hh]));
+      float f_g = sigmoidf_(get_gate(&grow[H + hh]));
+      float g_g = cell_act_<ACT>(get_gate(&grow[2 * H + hh]));
+      float o_g = sigmoidf_(get_gate(&grow[3 * H + hh]));
       float cc = f_g * cS[row * H + hh] + i_g * g_g;
-      float hv = o_g * fast_tanhf_(cc);
+      float hv = o_g * cell_act_<ACT>(cc);
       cS[row * H + hh] = cc;
       hxS[row * LDKc + hh] = lf2bf(hv);
       if (row < rows_here) {
@@ -1799,11 +1839,32 @@ struct ScanLaunch {
   int last_only = -1;
 };
 thread_local ScanLaunch g_last_launch;
+// cell activation of that launch, kept beside the record (whose five
+// fields are compared whole); "tanh" for every tanh-only family
+thread_local const char* g_last_act = "tanh";
+
+inline const char* act_name(int act) {
+  switch (act) {
+    case CELL_LINEAR: return "linear";
+    case CELL_RELU: return "relu";
+    case CELL_SIGMOID: return "sigmoid";
+    default: return "tanh";
+  }
+}
+
+inline void check_act(int64_t act) {
+  TORCH_CHECK(act >= CELL_LINEAR && act <= CELL_SIGMOID,
+              "unknown LSTM cell activation code ", act);
+}
 
 inline void note_launch(const char* family, int rows, int hf = 0,
-                        int has_dx = -1, int last_only = -1) {
+                        int has_dx = -1, int last_only = -1,
+                        int act = CELL_TANH) {
   g_last_launch = ScanLaunch{family, rows, hf, has_dx, last_only};
+  g_last_act = act_name(act);
 }
+
+std::string last_scan_activation() { return std::string(g_last_act); }
 
 std::tuple<std::string, int, int, int, int> last_scan_launch() {
   const ScanLaunch& l = g_last_launch;
@@ -1930,11 +1991,14 @@ std::vector<torch::Tensor> lstm_seq_fwd_fused(torch::Tensor xseq,
                                               torch::Tensor Wx,
                                               torch::Tensor Wh,
                                               torch::Tensor bias,
-                                              bool store_aux) {
+                                              bool store_aux, int64_t act) {
   // xseq [G,B,T,F]; Wx [G,F,4H]; Wh [G,H,4H]; bias [G,4H].
   // Computes the x-side gate GEMM inside the scan (see kernel note).
+  // This is the only forward scan with a cell activation parameter,
+  // and an unsupported geometry raises for every act.
   TORCH_CHECK(xseq.is_cuda() && xseq.dim() == 4,
               "xseq must be [G,B,T,F] on GPU");
+  check_act(act);
   auto xc = xseq.to(torch::kBFloat16).contiguous();
   auto Wxc = Wx.to(torch::kBFloat16);
   auto Whc = Wh.to(torch::kBFloat16);
@@ -1955,9 +2019,12 @@ std::vector<torch::Tensor> lstm_seq_fwd_fused(torch::Tensor xseq,
   auto gacts = store_aux ? torch::empty({G, B, T, H4}, xc.options())
                          : torch::empty({1}, xc.options());
   int rows = pick_rows(G, B);
+  // the pre-activation tile is fp32 for a non-tanh act (gate_tile_t)
+  const size_t gate_bytes = act == CELL_TANH ? 2 : 4;
   auto lds_for = [&](int r) {
     return (size_t)H4 * LDKc * 2 + (size_t)r * LDKc * 2 +
-           (size_t)r * ldg * 2 + (size_t)ldg * 2 + (size_t)r * H * 4;
+           (size_t)r * ldg * gate_bytes + (size_t)ldg * 2 +
+           (size_t)r * H * 4;
   };
   while (rows > 16 && lds_for(rows) > 160 * 1024) rows /= 2;
   size_t lds = lds_for(rows);
@@ -1970,20 +2037,30 @@ std::vector<torch::Tensor> lstm_seq_fwd_fused(torch::Tensor xseq,
   auto hp = (bf16*)hs.data_ptr();
   auto cp = cs.data_ptr<float>();
   auto gp = (bf16*)gacts.data_ptr();
-  #define V4_LAUNCH(R, S)                                              \
-    hipLaunchKernelGGL((lstm_seq_fwd_v4_kernel<R, S>), dim3(blocks),   \
-                       dim3(256), lds, stream, xp, wp, bp, hp, cp, gp, \
+  #define V4_LAUNCH(R, S, A)                                            \
+    hipLaunchKernelGGL((lstm_seq_fwd_v4_kernel<R, S, A>), dim3(blocks), \
+                       dim3(256), lds, stream, xp, wp, bp, hp, cp, gp,  \
                        B, T, H, F, ldg)
-  note_launch("fwd_v4", rows);
-  if (store_aux) {
-    if (rows == 64) V4_LAUNCH(64, true);
-    else if (rows == 32) V4_LAUNCH(32, true);
-    else V4_LAUNCH(16, true);
-  } else {
-    if (rows == 64) V4_LAUNCH(64, false);
-    else if (rows == 32) V4_LAUNCH(32, false);
-    else V4_LAUNCH(16, false);
+  #define V4_ROWS(S, A)                                                 \
+    do {                                                                \
+      if (rows == 64) V4_LAUNCH(64, S, A);                              \
+      else if (rows == 32) V4_LAUNCH(32, S, A);                         \
+      else V4_LAUNCH(16, S, A);                                         \
+    } while (0)
+  #define V4_AUX(A)                                                     \
+    do {                                                                \
+      if (store_aux) V4_ROWS(true, A);                                  \
+      else V4_ROWS(false, A);                                           \
+    } while (0)
+  note_launch("fwd_v4", rows, 0, -1, -1, (int)act);
+  switch ((int)act) {
+    case CELL_LINEAR: V4_AUX(CELL_LINEAR); break;
+    case CELL_RELU: V4_AUX(CELL_RELU); break;
+    case CELL_SIGMOID: V4_AUX(CELL_SIGMOID); break;
+    default: V4_AUX(CELL_TANH); break;
   }
+  #undef V4_AUX
+  #undef V4_ROWS
   #undef V4_LAUNCH
   if (store_aux) return {hs, cs, gacts};
   return {hs};
@@ -2129,15 +2206,25 @@ inline int pipe_rows(int rows, int T, int H, int F, bool has_dx, int ldg,
   return pipe_lds(rows, H, F, ldg, last_only) <= 160 * 1024 ? rows : 0;
 }
 
-#define GORDO_PIPE_LAUNCH(R, DX, LO)                                       \
-  hipLaunchKernelGGL((lstm_seq_bwd_pipe_kernel<R, DX, LO>), dim3(blocks),  \
-                     dim3(256), lds, stream, dp, gp, cp, whp, wxp, dgp,    \
-                     dxp, B, T, H, F, ldg)
+#define GORDO_PIPE_LAUNCH(R, DX, LO, A)                                    \
+  hipLaunchKernelGGL((lstm_seq_bwd_pipe_kernel<R, DX, LO, A>),             \
+                     dim3(blocks), dim3(256), lds, stream, dp, gp, cp,     \
+                     whp, wxp, dgp, dxp, B, T, H, F, ldg)
+#define GORDO_PIPE_ROWS_A(DX, LO, A)                                       \
+  do {                                                                     \
+    if (rows == 64) GORDO_PIPE_LAUNCH(64, DX, LO, A);                      \
+    else if (rows == 32) GORDO_PIPE_LAUNCH(32, DX, LO, A);                 \
+    else GORDO_PIPE_LAUNCH(16, DX, LO, A);                                 \
+  } while (0)
+// the cell activation `act` (an int in scope) picks the instantiation
 #define GORDO_PIPE_ROWS(DX, LO)                                            \
   do {                                                                     \
-    if (rows == 64) GORDO_PIPE_LAUNCH(64, DX, LO);                         \
-    else if (rows == 32) GORDO_PIPE_LAUNCH(32, DX, LO);                    \
-    else GORDO_PIPE_LAUNCH(16, DX, LO);                                    \
+    switch (act) {                                                         \
+      case CELL_LINEAR: GORDO_PIPE_ROWS_A(DX, LO, CELL_LINEAR); break;     \
+      case CELL_RELU: GORDO_PIPE_ROWS_A(DX, LO, CELL_RELU); break;         \
+      case CELL_SIGMOID: GORDO_PIPE_ROWS_A(DX, LO, CELL_SIGMOID); break;   \
+      default: GORDO_PIPE_ROWS_A(DX, LO, CELL_TANH); break;                \
+    }                                                                      \
   } while (0)
 
 inline void check_out(const torch::Tensor& out, const torch::Tensor& like,
@@ -2153,10 +2240,13 @@ inline void check_out(const torch::Tensor& out, const torch::Tensor& like,
 std::vector<torch::Tensor> lstm_seq_bwd_fused_impl(
     torch::Tensor dSeq, torch::Tensor gacts, torch::Tensor cs,
     torch::Tensor Wh, torch::Tensor Wx, bool last_only,
-    c10::optional<torch::Tensor> dG_out, c10::optional<torch::Tensor> dX_out) {
+    c10::optional<torch::Tensor> dG_out, c10::optional<torch::Tensor> dX_out,
+    int64_t act64) {
   // returns {dG, dX}: the reverse scan with dSeq_t = dG_t @ Wx^T
   // fused in (see kernel note). Geometry: H <= 64, F <= 128.
   TORCH_CHECK(gacts.is_cuda() && gacts.dim() == 4, "gacts must be [G,B,T,4H]");
+  check_act(act64);
+  const int act = (int)act64;
   auto dc = dSeq.to(torch::kBFloat16).contiguous();
   auto gc = gacts.to(torch::kBFloat16).contiguous();
   auto ccs = cs.to(torch::kFloat32).contiguous();
@@ -2183,11 +2273,16 @@ std::vector<torch::Tensor> lstm_seq_bwd_fused_impl(
     rows = prow;
     size_t lds = pipe_lds(rows, H, F, ldg, last_only);
     int blocks = G * ((B + rows - 1) / rows);
-    note_launch("bwd_pipe", rows, 0, 1, last_only ? 1 : 0);
+    note_launch("bwd_pipe", rows, 0, 1, last_only ? 1 : 0, act);
     if (last_only) GORDO_PIPE_ROWS(true, true);
     else GORDO_PIPE_ROWS(true, false);
     return {dG, dX};
   }
+  // only the pipelined kernel takes a cell activation
+  TORCH_CHECK(act == CELL_TANH, "lstm_seq_bwd_fused: cell activation '",
+              act_name(act), "' needs the pipelined kernel (H % 8 == 0, "
+              "8 <= H <= 64, F % 8 == 0, 8 <= F <= 128, T < 2^17, "
+              "GORDO_LSTM_PIPE != 0)");
   auto lds_for = [&](int r) {
     return (size_t)H * ldg * 2 + (size_t)F * ldg * 2 +
            (size_t)r * ldg * 2 + (size_t)r * LDK * 2 + (size_t)r * H * 4;
@@ -2215,9 +2310,9 @@ std::vector<torch::Tensor> lstm_seq_bwd_fused_impl(
 
 std::vector<torch::Tensor> lstm_seq_bwd_fused(
     torch::Tensor dSeq, torch::Tensor gacts, torch::Tensor cs,
-    torch::Tensor Wh, torch::Tensor Wx, bool last_only) {
+    torch::Tensor Wh, torch::Tensor Wx, bool last_only, int64_t act) {
   return lstm_seq_bwd_fused_impl(dSeq, gacts, cs, Wh, Wx, last_only,
-                                 c10::nullopt, c10::nullopt);
+                                 c10::nullopt, c10::nullopt, act);
 }
 
 // the same scan writing into caller-provided dG / dX (tests place them
@@ -2225,19 +2320,28 @@ std::vector<torch::Tensor> lstm_seq_bwd_fused(
 void lstm_seq_bwd_fused_out(torch::Tensor dSeq, torch::Tensor gacts,
                             torch::Tensor cs, torch::Tensor Wh,
                             torch::Tensor Wx, bool last_only,
-                            torch::Tensor dG, torch::Tensor dX) {
-  lstm_seq_bwd_fused_impl(dSeq, gacts, cs, Wh, Wx, last_only, dG, dX);
+                            torch::Tensor dG, torch::Tensor dX,
+                            int64_t act) {
+  lstm_seq_bwd_fused_impl(dSeq, gacts, cs, Wh, Wx, last_only, dG, dX, act);
 }
 
 torch::Tensor lstm_seq_bwd_v3_impl(torch::Tensor dSeq, torch::Tensor gacts,
                                    torch::Tensor cs, torch::Tensor Wh,
                                    bool last_only,
-                                   c10::optional<torch::Tensor> dG_out) {
+                                   c10::optional<torch::Tensor> dG_out,
+                                   int64_t act64) {
   // identical contract to lstm_seq_bwd; pipelined kernel, always the
   // barriered layout (A/B-tested against v1 on the same shapes).
   // H > 64 routes to the big-H kernel (no v3 there).
   TORCH_CHECK(gacts.is_cuda() && gacts.dim() == 4, "gacts must be [G,B,T,4H]");
+  check_act(act64);
+  const int act = (int)act64;
+  const char* need_pipe =
+      "' needs the pipelined kernel (H % 8 == 0, 8 <= H <= 64, T < 2^17, "
+      "GORDO_LSTM_PIPE != 0)";
   if (gacts.size(3) / 4 > 64) {
+    TORCH_CHECK(act == CELL_TANH, "lstm_seq_bwd_v3: cell activation '",
+                act_name(act), need_pipe);
     TORCH_CHECK(!dG_out, "no out variant on the big-H path");
     return lstm_seq_bwd_big(dSeq, gacts, cs, Wh, last_only);
   }
@@ -2265,11 +2369,13 @@ torch::Tensor lstm_seq_bwd_v3_impl(torch::Tensor dSeq, torch::Tensor gacts,
     const bf16* wxp = nullptr;
     auto dgp = (bf16*)dG.data_ptr();
     bf16* dxp = nullptr;
-    note_launch("bwd_pipe", rows, 0, 0, last_only ? 1 : 0);
+    note_launch("bwd_pipe", rows, 0, 0, last_only ? 1 : 0, act);
     if (last_only) GORDO_PIPE_ROWS(false, true);
     else GORDO_PIPE_ROWS(false, false);
     return dG;
   }
+  TORCH_CHECK(act == CELL_TANH, "lstm_seq_bwd_v3: cell activation '",
+              act_name(act), need_pipe);
   size_t lds = (size_t)H * ldg * 2 + (size_t)rows * ldg * 2 +
                (size_t)rows * LDK * 2 + (size_t)rows * H * 4;
   TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded");
@@ -2299,14 +2405,15 @@ torch::Tensor lstm_seq_bwd_v3_impl(torch::Tensor dSeq, torch::Tensor gacts,
 
 torch::Tensor lstm_seq_bwd_v3(torch::Tensor dSeq, torch::Tensor gacts,
                               torch::Tensor cs, torch::Tensor Wh,
-                              bool last_only) {
-  return lstm_seq_bwd_v3_impl(dSeq, gacts, cs, Wh, last_only, c10::nullopt);
+                              bool last_only, int64_t act) {
+  return lstm_seq_bwd_v3_impl(dSeq, gacts, cs, Wh, last_only, c10::nullopt,
+                              act);
 }
 
 void lstm_seq_bwd_v3_out(torch::Tensor dSeq, torch::Tensor gacts,
                          torch::Tensor cs, torch::Tensor Wh, bool last_only,
-                         torch::Tensor dG) {
-  lstm_seq_bwd_v3_impl(dSeq, gacts, cs, Wh, last_only, dG);
+                         torch::Tensor dG, int64_t act) {
+  lstm_seq_bwd_v3_impl(dSeq, gacts, cs, Wh, last_only, dG, act);
 }
 
 torch::Tensor lstm_seq_bwd(torch::Tensor dSeq, torch::Tensor gacts,
@@ -2379,6 +2486,7 @@ torch::Tensor lstm_seq_bwd(torch::Tensor dSeq, torch::Tensor gacts,
 }
 
 #undef GORDO_PIPE_ROWS
+#undef GORDO_PIPE_ROWS_A
 #undef GORDO_PIPE_LAUNCH
 
 }  // namespace gordo_lstm

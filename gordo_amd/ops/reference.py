@@ -282,22 +282,24 @@ def adam_step(
 
 
 def lstm_pointwise_fwd(
-    gates: torch.Tensor, c_prev: torch.Tensor
+    gates: torch.Tensor, c_prev: torch.Tensor, act="tanh"
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """
     LSTM cell pointwise math (Keras gate order i, f, c(g), o).
 
     gates: [G, B, 4H] pre-activation (x@Wx + h@Wh + b).
     Returns (h, c, gact) where gact = activated gates [G, B, 4H]
-    saved for the backward pass.
+    saved for the backward pass. ``act`` is the cell activation φ of
+    the candidate gate and of φ(c); i, f, o stay sigmoid.
     """
+    act = act_code(act)
     H = gates.shape[-1] // 4
     i = torch.sigmoid(gates[..., 0 * H : 1 * H])
     f = torch.sigmoid(gates[..., 1 * H : 2 * H])
-    g = torch.tanh(gates[..., 2 * H : 3 * H])
+    g = apply_act(gates[..., 2 * H : 3 * H], act)
     o = torch.sigmoid(gates[..., 3 * H : 4 * H])
     c = f * c_prev + i * g
-    h = o * torch.tanh(c)
+    h = o * apply_act(c, act)
     gact = torch.cat([i, f, g, o], dim=-1)
     return h, c, gact
 
@@ -308,14 +310,18 @@ def lstm_pointwise_bwd(
     gact: torch.Tensor,
     c: torch.Tensor,
     c_prev: torch.Tensor,
+    act="tanh",
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """
     Backward of the pointwise cell math.
 
     Inputs: dh (grad wrt h_t), dc_next (grad wrt c_t from t+1),
     gact = [i,f,g,o] activated, c = c_t, c_prev = c_{t-1}.
-    Returns (dgates_pre [G,B,4H], dc_prev [G,B,H]).
+    Returns (dgates_pre [G,B,4H], dc_prev [G,B,H]). Both derivatives
+    of the cell activation ``act`` come from stored values: φ'(z_g)
+    from g, φ'(c) from φ(c).
     """
+    act = act_code(act)
     H = dh.shape[-1]
     i, f, g, o = (
         gact[..., 0 * H : 1 * H],
@@ -323,9 +329,9 @@ def lstm_pointwise_bwd(
         gact[..., 2 * H : 3 * H],
         gact[..., 3 * H : 4 * H],
     )
-    tanh_c = torch.tanh(c)
-    do = dh * tanh_c
-    dc = dc_next + dh * o * (1.0 - tanh_c * tanh_c)
+    phi_c = apply_act(c, act)
+    do = dh * phi_c
+    dc = dc_next + dh * o * act_grad_from_output(phi_c, act)
     di = dc * g
     df = dc * c_prev
     dg = dc * i
@@ -334,7 +340,7 @@ def lstm_pointwise_bwd(
         [
             di * i * (1.0 - i),
             df * f * (1.0 - f),
-            dg * (1.0 - g * g),
+            dg * act_grad_from_output(g, act),
             do * o * (1.0 - o),
         ],
         dim=-1,
@@ -351,7 +357,8 @@ def lstm_pointwise_bwd(
 # output) and dX. c, dc and the dh carry stay unrounded. Inputs are
 # used as passed: callers wanting the kernel's view pass bf16-rounded
 # tensors. With ``round_points=False`` the functions are the exact
-# (differentiable) recurrence and its analytic gradient.
+# (differentiable) recurrence and its analytic gradient. ``act`` is the
+# cell activation φ (g = φ(z_g), h = o·φ(c)); the gates stay sigmoid.
 # ---------------------------------------------------------------------------
 
 
@@ -359,8 +366,9 @@ def _bf16_round(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.bfloat16).to(t.dtype)
 
 
-def _scan_fwd(gate_x, B, T, Wh, b, dtype, round_points):
+def _scan_fwd(gate_x, B, T, Wh, b, dtype, round_points, act="tanh"):
     """gate_x(t) -> x-side pre-activation [G,B,4H] of step t."""
+    act = act_code(act)
     rnd = _bf16_round if round_points else (lambda t: t)
     Wh = Wh.to(dtype)
     G, H = Wh.shape[0], Wh.shape[1]
@@ -373,40 +381,42 @@ def _scan_fwd(gate_x, B, T, Wh, b, dtype, round_points):
             gates = gates + b.to(dtype).unsqueeze(1)
         i = torch.sigmoid(gates[..., 0 * H:1 * H])
         f = torch.sigmoid(gates[..., 1 * H:2 * H])
-        g = torch.tanh(gates[..., 2 * H:3 * H])
+        g = apply_act(gates[..., 2 * H:3 * H], act)
         o = torch.sigmoid(gates[..., 3 * H:4 * H])
         c = f * c + i * g
-        h = rnd(o * torch.tanh(c))
+        h = rnd(o * apply_act(c, act))
         hs.append(h)
         cs.append(c)
         gas.append(rnd(torch.cat([i, f, g, o], dim=-1)))
     return torch.stack(hs, 2), torch.stack(cs, 2), torch.stack(gas, 2)
 
 
-def lstm_seq_fwd_ref(xW, Wh, *, dtype=torch.float64, round_points=True):
+def lstm_seq_fwd_ref(xW, Wh, *, dtype=torch.float64, round_points=True,
+                     act="tanh"):
     """Forward scan over precomputed x-side gates xW [G,B,T,4H] with
     Wh [G,H,4H] (gate order i, f, g, o; h_0 = c_0 = 0). Returns
     ``(hs [G,B,T,H], cs [G,B,T,H], gacts [G,B,T,4H])`` in ``dtype``."""
     xW = xW.to(dtype)
     return _scan_fwd(lambda t: xW[:, :, t], xW.shape[1], xW.shape[2], Wh,
-                     None, dtype, round_points)
+                     None, dtype, round_points, act)
 
 
 def lstm_seq_fwd_fused_ref(x, Wx, Wh, b, *, dtype=torch.float64,
-                           round_points=True):
+                           round_points=True, act="tanh"):
     """Same scan with the x-side product x_t @ Wx + b formed inside the
     step and added unrounded (x [G,B,T,F], Wx [G,F,4H], b [G,4H])."""
     x, Wx = x.to(dtype), Wx.to(dtype)
     return _scan_fwd(lambda t: torch.bmm(x[:, :, t], Wx), x.shape[1],
-                     x.shape[2], Wh, b, dtype, round_points)
+                     x.shape[2], Wh, b, dtype, round_points, act)
 
 
 def lstm_seq_bwd_ref(dSeq, gacts, cs, Wh, last_only, *, Wx=None,
-                     dtype=torch.float64, round_points=True):
+                     dtype=torch.float64, round_points=True, act="tanh"):
     """Reverse (BPTT) scan: pre-activation gate grads dG [G,B,T,4H]
     from upstream grads on the h sequence (dSeq [G,B,T,H], or [G,B,H]
     on h_{T-1} alone when ``last_only``) and the forward's ``gacts`` /
     ``cs``. With ``Wx`` [G,F,4H] also returns dX = dG @ Wx^T."""
+    act = act_code(act)
     rnd = _bf16_round if round_points else (lambda t: t)
     dSeq, gacts, cs, Wh = (t.to(dtype) for t in (dSeq, gacts, cs, Wh))
     G, B, T, H4 = gacts.shape
@@ -427,12 +437,12 @@ def lstm_seq_bwd_ref(dSeq, gacts, cs, Wh, last_only, *, Wx=None,
         i, f = ga[..., 0 * H:1 * H], ga[..., 1 * H:2 * H]
         g, o = ga[..., 2 * H:3 * H], ga[..., 3 * H:4 * H]
         c_prev = cs[:, :, t - 1] if t > 0 else torch.zeros_like(dc)
-        tc = torch.tanh(cs[:, :, t])
-        dc = dc + dh * o * (1.0 - tc * tc)
+        tc = apply_act(cs[:, :, t], act)
+        dc = dc + dh * o * act_grad_from_output(tc, act)
         dg_t = rnd(torch.cat([
             dc * g * i * (1.0 - i),
             dc * c_prev * f * (1.0 - f),
-            dc * i * (1.0 - g * g),
+            dc * i * act_grad_from_output(g, act),
             dh * tc * o * (1.0 - o),
         ], dim=-1))
         dc = dc * f
@@ -646,28 +656,37 @@ def mse_bwd_ref(Y, T, real_n: int = -1):
     return _both(run)
 
 
-def lstm_pointwise_fwd_ref(gates, c_prev):
+def _cell_act(z, act):
+    """φ(z) with the sigmoid spelled like the gates' (1/(1+exp(-z)))."""
+    if act == ACT_SIGMOID:
+        return 1.0 / (1.0 + torch.exp(-z))
+    return apply_act(z, act)
+
+
+def lstm_pointwise_fwd_ref(gates, c_prev, act="tanh"):
     """One LSTM cell step from pre-activations [.., 4H] (order i, f,
     g, o) and c_prev [.., H]: ``((h, c, gact) fp64, (...) fp32)``,
-    nothing rounded to bf16."""
+    nothing rounded to bf16. ``act`` is the cell activation."""
+    act = act_code(act)
     H = gates.shape[-1] // 4
 
     def run(dt):
         z, cp = gates.to(dt), c_prev.to(dt)
         i = 1.0 / (1.0 + torch.exp(-z[..., 0 * H:1 * H]))
         f = 1.0 / (1.0 + torch.exp(-z[..., 1 * H:2 * H]))
-        g = torch.tanh(z[..., 2 * H:3 * H])
+        g = _cell_act(z[..., 2 * H:3 * H], act)
         o = 1.0 / (1.0 + torch.exp(-z[..., 3 * H:4 * H]))
         c = f * cp + i * g
-        return o * torch.tanh(c), c, torch.cat([i, f, g, o], dim=-1)
+        return o * _cell_act(c, act), c, torch.cat([i, f, g, o], dim=-1)
 
     return _both(run)
 
 
-def lstm_pointwise_bwd_ref(dh, dc_next, gact, c, c_prev):
+def lstm_pointwise_bwd_ref(dh, dc_next, gact, c, c_prev, act="tanh"):
     """Gradient of that step with respect to the pre-activations and
     c_prev, from the ACTIVATED gates as given (the kernel reads them
     back as bf16): ``((dgates, dc_prev) fp64, (...) fp32)``."""
+    act = act_code(act)
     H = dh.shape[-1]
 
     def run(dt):
@@ -675,12 +694,12 @@ def lstm_pointwise_bwd_ref(dh, dc_next, gact, c, c_prev):
         i, f = ga[..., 0 * H:1 * H], ga[..., 1 * H:2 * H]
         g, o = ga[..., 2 * H:3 * H], ga[..., 3 * H:4 * H]
         d, cc, cp = dh.to(dt), c.to(dt), c_prev.to(dt)
-        tc = torch.tanh(cc)
-        dc = dc_next.to(dt) + d * o * (1.0 - tc * tc)
+        tc = _cell_act(cc, act)
+        dc = dc_next.to(dt) + d * o * act_grad_from_output(tc, act)
         dgates = torch.cat([
             dc * g * i * (1.0 - i),
             dc * cp * f * (1.0 - f),
-            dc * i * (1.0 - g * g),
+            dc * i * act_grad_from_output(g, act),
             d * tc * o * (1.0 - o),
         ], dim=-1)
         return dgates, dc * f
