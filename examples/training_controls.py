@@ -38,6 +38,35 @@ def main():
           f"val_loss {hist['val_loss'][-1]:.5f}")
     assert len(hist["loss"]) < 100
     assert np.isfinite(hist["val_loss"]).all()
+    per_model_stopping()
+
+
+def per_model_stopping():
+    """In a pack every model stops at its own patience: a noise model
+    stalls long before a sine model does, and each keeps the history
+    (and weights) of its own run. ``restore_best_weights`` goes back to
+    each model's best epoch."""
+    import torch
+
+    from gordo_amd.engine.pack import DensePack
+    from gordo_amd.machine.model.models import _history_for_model
+
+    spec = KerasAutoEncoder(kind="feedforward_hourglass").build_pack_spec(8, 8)
+    t = np.linspace(0, 12, 512)
+    sines = np.stack([np.sin(t + p) for p in np.linspace(0, 2, 8)], axis=1)
+    noise = np.random.default_rng(1).random((512, 8)) * 0.5
+    X = torch.tensor(np.stack([noise, 2 * sines]).astype("float32"))
+    pack = DensePack(spec, G=2, seeds=[1, 2])
+    X = X.to(pack.device)
+    hist = pack.fit(
+        X, X.clone(), epochs=60, batch_size=64,
+        early_stopping={"monitor": "loss", "patience": 2, "min_delta": 5e-3,
+                        "restore_best_weights": True},
+    )
+    print(f"pack ran {len(hist['loss'])} epochs; per model: "
+          f"{hist.epochs_run}, best epochs {hist.best_epoch}")
+    for g in range(2):
+        assert len(_history_for_model(hist, g)["loss"]) == hist.epochs_run[g]
 
 
 if __name__ == "__main__":

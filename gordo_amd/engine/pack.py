@@ -31,9 +31,24 @@ import numpy as np
 import torch
 
 from .. import ops
+from .early_stop import EarlyStopState
 from .spec import ModelSpec
 
 logger = logging.getLogger(__name__)
+
+
+class FitHistory(dict):
+    """The history ``BasePack.fit`` returns: the rectangular
+    ``{key: [[G values] per epoch]}`` dict, plus ``epochs_run``, the
+    number of epochs each model itself trained for (its stopped epoch
+    + 1 under early stopping, else the epochs of the fit). Rows past
+    ``epochs_run[g]`` hold model g's frozen-weight values.
+    ``best_epoch`` (early stopping only) is each model's epoch of the
+    best monitored value: the one ``restore_best_weights`` goes back
+    to."""
+
+    epochs_run: Optional[List[int]] = None
+    best_epoch: Optional[List[int]] = None
 
 
 def _compute_dtype(device: torch.device) -> torch.dtype:
@@ -112,6 +127,11 @@ class _ParamStore:
         self.cviews: Dict[str, torch.Tensor] = {}
         self.gviews: Dict[str, torch.Tensor] = {}
         self.step_count = 0
+        # per-model early stopping: int32 [G] device mask of the models
+        # that still train. None (the unmasked kernels run) until a fit
+        # with early stopping and G > 1 sets it.
+        self.active: Optional[torch.Tensor] = None
+        self._segments: Optional[torch.Tensor] = None
 
     def declare(self, name: str, shape: Tuple[int, ...],
                 logical: Optional[Tuple[int, ...]] = None):
@@ -155,6 +175,44 @@ class _ParamStore:
                 else self.views[name]
             )
 
+    @property
+    def segments(self) -> torch.Tensor:
+        """Segment table of the flat buffer for the masked ops: tensor
+        s is [G, per_s] at off_s, so model g owns off_s + g*per_s
+        onwards. Built once, when a fit first needs it: a pack that
+        never stops a model early uploads nothing."""
+        if self._segments is None:
+            self._segments = ops.segment_table(
+                [self._offsets[name][0] for name, _ in self._shapes],
+                [self._offsets[name][1] // max(int(shape[0]), 1)
+                 for name, shape in self._shapes],
+                self.device,
+            )
+        return self._segments
+
+    def set_active(self, active) -> None:
+        """Upload the [G] mask of the models that still train (None:
+        back to the unmasked step)."""
+        self.active = (
+            None if active is None else self.model_mask(active)
+        )
+
+    def model_mask(self, mask) -> torch.Tensor:
+        """A host bool [G] mask as the int32 device tensor the masked
+        ops take."""
+        return torch.as_tensor(
+            np.asarray(mask, dtype=np.int32), device=self.device
+        )
+
+    def copy_models(self, dst: torch.Tensor, src: torch.Tensor, mask,
+                    mirror: bool = False) -> None:
+        """dst <- src for the flat-buffer slices of the masked models;
+        ``mirror`` also refreshes their slices of the bf16 mirror."""
+        ops.masked_copy(
+            dst, src, self.model_mask(mask), self.segments,
+            self.plp if mirror else None,
+        )
+
     def sync_lp(self):
         if self.plp is not None:
             self.plp.copy_(self.p32)
@@ -171,12 +229,15 @@ class _ParamStore:
         )
 
     def optimizer_step(self):
-        """One step of the spec's optimizer over the whole buffer."""
+        """One step of the spec's optimizer over the whole buffer, or,
+        while ``active`` is set, over the models that still train."""
         self.step_count += 1
+        # active None (no early stopping, or G = 1): the unmasked kernels
         ops.optimizer_step(
             self.optimizer_kind, self.p32, self.g32, self.m, self.v,
             self.vhat, self.optimizer_params, self.step_count, self.plp,
-            step_buf=self.step_buf,
+            step_buf=self.step_buf, active=self.active,
+            segments=None if self.active is None else self.segments,
         )
 
     def _init_slots(self):
@@ -388,6 +449,8 @@ class BasePack:
             self._graph_enabled
             and os.environ.get("GORDO_HIPGRAPH", "0") == "1"
             and self.device.type == "cuda"
+            # a masked step (per-model early stopping) runs eagerly
+            and self.store.active is None
         ):
             # _graph_enabled False (set per-instance after a capture
             # failure) wins; otherwise the env is re-read so flipping
@@ -547,13 +610,16 @@ class BasePack:
         "accuracy": ...}. ``loss`` is the spec's configured loss and
         ``accuracy`` the Keras metric of that name (argmax agreement
         per row; binary accuracy for one output column), accumulated
-        over the epoch's batches as Keras does.
+        over the epoch's batches as Keras does. ``early_stopping``
+        (``engine.early_stop``) stops every model at its own patience;
+        the returned ``FitHistory`` says in ``epochs_run`` how many
+        epochs each model trained for.
         """
         if self.pad8:
             X = self._pad_features(X, self._logical_in)
             Y = self._pad_features(Y, self._logical_out)
         G, N = X.shape[0], X.shape[1]
-        history: Dict[str, list] = {"loss": [], "accuracy": []}
+        history = FitHistory({"loss": [], "accuracy": []})
         n_all = self._n_samples(N)
         # keras validation_split semantics: the LAST fraction of samples
         # (in input order, before shuffling) is held out; history gains
@@ -565,21 +631,45 @@ class BasePack:
             if n_train < n_all:
                 history["val_loss"] = []
                 history["val_accuracy"] = []
-        n_val = n_all - n_train
-        # EarlyStopping (keras semantics, restore_best_weights=False):
-        # training ends when EVERY model in the pack has gone `patience`
-        # epochs without improving its train loss by `min_delta` (models
-        # train in lockstep, so the group stops when all have stalled;
-        # for G=1 this is exactly the keras behavior on `loss`).
-        es_patience = es_min_delta = None
+        # EarlyStopping (the Keras rule, engine/early_stop.py): every
+        # model stops at its OWN patience. A stopped model still runs
+        # forward and backward in lockstep with the pack, but the masked
+        # optimizer step leaves its parameters, optimizer state and
+        # mirror alone, so its weights are those of a solo fit. The fit
+        # ends when every model has ended.
+        es: Optional[EarlyStopState] = None
         if early_stopping is not None:
-            es_patience = int(early_stopping.get("patience", 0))
-            es_min_delta = float(early_stopping.get("min_delta", 0.0))
-            es_best = np.full(G, np.inf)
-            es_wait = np.zeros(G, dtype=np.int64)
+            es = EarlyStopState(G, early_stopping)
+            if G > 1:
+                self.store.set_active(np.ones(G, dtype=bool))
+        try:
+            epochs_done = self._fit_epochs(
+                X, Y, epochs, batch_size, shuffle, verbose, history,
+                n_train, n_all, es,
+            )
+        finally:
+            self.store.set_active(None)
+        if es is None:
+            history.epochs_run = [epochs_done] * G
+        else:
+            history.epochs_run = [
+                int(es.stopped_epoch[g]) + 1 if es.ended[g] else epochs_done
+                for g in range(G)
+            ]
+            history.best_epoch = [int(e) for e in es.best_epoch]
+        return history
+
+    def _fit_epochs(self, X, Y, epochs, batch_size, shuffle, verbose,
+                    history, n_train, n_all, es) -> int:
+        """The epoch loop of ``fit``; returns the number of epochs run."""
+        G = X.shape[0]
+        n_val = n_all - n_train
+        best_p32: Optional[torch.Tensor] = None
         n_batches = max(1, math.ceil(n_train / batch_size))
         gens = [torch.Generator().manual_seed(int(s) & 0x7FFFFFFF) for s in self.seeds]
+        epochs_done = 0
         for epoch in range(epochs):
+            epochs_done = epoch + 1
             if shuffle:
                 perm = torch.stack(
                     [torch.randperm(n_train, generator=g) for g in gens]
@@ -640,24 +730,37 @@ class BasePack:
                     "epoch %d/%d mean-loss=%.6g", epoch + 1, epochs,
                     float(np.mean(epoch_loss)),
                 )
-            if es_patience is not None:
-                monitor_val = (
-                    str((early_stopping or {}).get("monitor", "loss"))
-                    .startswith("val") and n_val > 0
-                )
-                losses = np.asarray(
-                    history["val_loss"][-1] if monitor_val else epoch_loss
-                )
-                improved = losses < (es_best - es_min_delta)
-                es_best = np.minimum(es_best, losses)
-                es_wait = np.where(improved, 0, es_wait + 1)
-                if epoch > 0 and (es_wait >= es_patience).all():
-                    if verbose:
-                        logger.info(
-                            "early stopping at epoch %d/%d", epoch + 1, epochs
-                        )
+            if es is None:
+                continue
+            upd = es.update(epoch, es.monitored(history))
+            if upd.capture.any():
+                # best weights of the models that improved
+                if best_p32 is None:
+                    best_p32 = torch.empty_like(self.store.p32)
+                self.store.copy_models(best_p32, self.store.p32, upd.capture)
+            if upd.stop.any():
+                self._restore_best(best_p32, upd.stop & es.has_best)
+                if verbose:
+                    logger.info(
+                        "early stopping at epoch %d/%d: models %s",
+                        epoch + 1, epochs, np.nonzero(upd.stop)[0].tolist(),
+                    )
+                if es.ended.all():
                     break
-        return history
+                if G > 1:  # the mask changed: upload it
+                    self.store.set_active(~es.ended)
+        if es is not None:
+            # models that ran to the epoch cap end here
+            self._restore_best(best_p32, ~es.ended & es.has_best)
+        return epochs_done
+
+    def _restore_best(self, best_p32, mask) -> None:
+        """The masked models' weights (and mirror) become their best
+        weights; optimizer state is not restored."""
+        if best_p32 is not None and mask.any():
+            self.store.copy_models(
+                self.store.p32, best_p32, mask, mirror=True
+            )
 
     def _n_samples(self, N: int) -> int:
         return N

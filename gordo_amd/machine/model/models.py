@@ -290,8 +290,13 @@ def _parse_early_stopping(callbacks) -> Optional[Dict[str, Any]]:
     """Extract EarlyStopping settings from a keras-style callbacks list
     (reference configs: [{"tensorflow.keras.callbacks.EarlyStopping":
     {"monitor": ..., "patience": ...}}]). Only EarlyStopping has an
-    engine analog; other callbacks are ignored. The engine has no
-    validation split, so val_* monitors fall back to train loss."""
+    engine analog; other callbacks are ignored. Without a validation
+    split, val_* monitors fall back to the train quantity.
+
+    ``restore_best_weights``, ``mode``, ``baseline`` and
+    ``start_from_epoch`` appear in the result only when the config
+    gives them (``engine.early_stop.EarlyStopState`` holds the
+    defaults and the rule); a ``mode`` outside min/max/auto raises."""
     for cb in callbacks or []:
         if isinstance(cb, str) and cb.rsplit(".", 1)[-1] == "EarlyStopping":
             return {"patience": 0, "min_delta": 0.0}
@@ -300,11 +305,31 @@ def _parse_early_stopping(callbacks) -> Optional[Dict[str, Any]]:
             if key.rsplit(".", 1)[-1] == "EarlyStopping":
                 params = cb[key] or {}
                 monitor = params.get("monitor", "val_loss")
-                return {
+                out = {
                     "monitor": str(monitor),
                     "patience": int(params.get("patience", 0)),
                     "min_delta": float(params.get("min_delta", 0.0)),
                 }
+                if "restore_best_weights" in params:
+                    out["restore_best_weights"] = bool(
+                        params["restore_best_weights"]
+                    )
+                if "mode" in params:
+                    mode = str(params["mode"])
+                    if mode not in ("auto", "min", "max"):
+                        raise ValueError(
+                            "EarlyStopping mode must be one of auto, min, "
+                            f"max; got {mode!r}"
+                        )
+                    out["mode"] = mode
+                if "baseline" in params:
+                    baseline = params["baseline"]
+                    out["baseline"] = (
+                        None if baseline is None else float(baseline)
+                    )
+                if "start_from_epoch" in params:
+                    out["start_from_epoch"] = int(params["start_from_epoch"])
+                return out
     return None
 
 
@@ -332,8 +357,12 @@ def _clean_fit_args(args: Dict[str, Any]) -> Dict[str, Any]:
 
 
 def _history_for_model(history: Dict[str, list], g: int) -> Dict[str, list]:
+    """Model g's lists of a pack history, cut to the epochs the model
+    itself ran (``history.epochs_run``, per-model early stopping)."""
+    epochs_run = getattr(history, "epochs_run", None)
+    n = None if epochs_run is None else int(epochs_run[g])
     return {
-        key: [float(epoch_vals[g]) for epoch_vals in values]
+        key: [float(epoch_vals[g]) for epoch_vals in values[:n]]
         for key, values in history.items()
     }
 

@@ -180,25 +180,63 @@ def loss_bwd(Y, T, loss, real_f: int, delta: float = 1.0,
     return ref.loss_bwd(Y, T, kind, int(real_f), float(delta), want_grad)
 
 
-# optimizer codes of train_ops.hip (plain Adam keeps adam_kernel)
+# optimizer codes of train_ops.hip (plain Adam keeps adam_kernel; it is
+# code 0 of the masked entry in masked_ops.hip)
 _OPT_SGD, _OPT_RMSPROP, _OPT_ADAGRAD, _OPT_ADAM_AMSGRAD, _OPT_ADAMAX = (
     1, 2, 3, 4, 5
 )
+_OPT_ADAM = 0
+
+
+def segment_table(offsets, sizes, device=None):
+    """int64 [2, S] segment table of a flat [S tensors of [G, size_s]]
+    buffer (row 0 offsets, row 1 per-model sizes) on ``device``: what
+    the masked ops take as ``segments`` / ``table``."""
+    return ref.segment_table(offsets, sizes, device)
+
+
+def masked_copy(dst, src, mask, table, dst_lp=None):
+    """Copy the slices of the models with ``mask[g] != 0`` from the
+    flat fp32 ``src`` to ``dst`` (and, rounded, into the bf16 mirror
+    ``dst_lp``); every other element of ``dst`` / ``dst_lp`` is left
+    untouched. ``mask`` is an int32 [G] tensor, ``table`` a
+    ``segment_table``, both on the buffers' device."""
+    if _on_gpu(dst):
+        return _require_hip().masked_copy(dst, src, mask, table, dst_lp)
+    return ref.masked_copy(dst, src, mask, table, dst_lp)
 
 
 def optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp=None,
-                   step_buf=None):
+                   step_buf=None, active=None, segments=None):
     """One fused optimizer step over the flat fp32 master buffer (+
     bf16 mirror refresh). ``kind``/``hyper`` are the spec's canonical
     optimizer name and complete ``optimizer_params``. On GPU the step
-    counter is read from the device ``step_buf`` (capturable)."""
+    counter is read from the device ``step_buf`` (capturable).
+
+    With ``active`` (int32 [G]) and ``segments`` (``segment_table``)
+    the step takes the masked entry: a model with ``active[g] == 0`` is
+    neither read nor written, an active one gets exactly the unmasked
+    arithmetic. Without ``active`` the unmasked kernels run."""
+    if active is not None and segments is None:
+        raise ValueError("a masked optimizer_step needs the segment table")
     if not _on_gpu(p):
+        if active is not None:
+            return ref.optimizer_step_masked(
+                kind, p, g, s0, s1, s2, hyper, step, p_lp, active, segments
+            )
         return ref.optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp)
     if step_buf is None:
         raise ValueError("GPU optimizer_step needs a device step_buf")
     h = hyper
     lr = float(h["learning_rate"])
     if kind == "adam" and not h.get("amsgrad"):
+        if active is not None:
+            return _require_hip().optimizer_step_masked(
+                _OPT_ADAM, p, g, s0, s1, None,
+                [lr, float(h["beta_1"]), float(h["beta_2"]),
+                 float(h["epsilon"])],
+                False, p_lp, step_buf, active, segments,
+            )
         return _require_hip().adam_step(
             p, g, s0, s1, lr, float(h["beta_1"]), float(h["beta_2"]),
             float(h["epsilon"]), int(step), p_lp, step_buf,
@@ -220,6 +258,11 @@ def optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp=None,
         vals = [lr, h["beta_1"], h["beta_2"], h["epsilon"]]
     else:
         raise ValueError(f"Unsupported optimizer {kind!r}")
+    if active is not None:
+        return _require_hip().optimizer_step_masked(
+            code, p, g, s0, s1, s2, [float(v) for v in vals], flag, p_lp,
+            step_buf, active, segments,
+        )
     return _require_hip().optimizer_step(
         code, p, g, s0, s1, s2, [float(v) for v in vals], flag, p_lp,
         step_buf,

@@ -1010,7 +1010,29 @@ void optimizer_step(int64_t kind, torch::Tensor p, torch::Tensor g,
                     torch::Tensor step_buf);
 }  // namespace gordo_train
 
+// per-model masked optimizer step and copy (masked_ops.hip)
+namespace gordo_masked {
+void optimizer_step_masked(int64_t kind, torch::Tensor p, torch::Tensor g,
+                           c10::optional<torch::Tensor> s0,
+                           c10::optional<torch::Tensor> s1,
+                           c10::optional<torch::Tensor> s2,
+                           std::vector<double> hyper, bool flag,
+                           c10::optional<torch::Tensor> plp,
+                           torch::Tensor step_buf, torch::Tensor active,
+                           torch::Tensor table);
+void masked_copy(torch::Tensor dst, torch::Tensor src, torch::Tensor mask,
+                 torch::Tensor table, c10::optional<torch::Tensor> dst_lp);
+}  // namespace gordo_masked
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("optimizer_step_masked", &gordo_masked::optimizer_step_masked,
+          "optimizer step (every kind, plain Adam = 0) over the models "
+          "with active[g] != 0 only");
+  mod.def("masked_copy", &gordo_masked::masked_copy, py::arg("dst"),
+          py::arg("src"), py::arg("mask"), py::arg("table"),
+          py::arg("dst_lp") = py::none(),
+          "copy the slices of the models with mask[g] != 0 (+ bf16 "
+          "mirror)");
   mod.def("loss_bwd", &gordo_train::loss_bwd,
           "fused per-model loss (mse/mae/huber/logcosh) + grad + "
           "accuracy count, one pass over (Y, T)");

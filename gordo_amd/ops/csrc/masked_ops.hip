@@ -1,0 +1,479 @@
+// Per-model masked forms of the flat-buffer ops (per-model early
+// stopping):
+//   optimizer_step_masked  every optimizer kind of adam_kernel /
+//                          opt_kernel<KIND>, skipping the models whose
+//                          active[g] == 0
+//   masked_copy            dst <- src (+ bf16 mirror) for the models
+//                          whose mask[g] != 0
+//
+// The flat buffer holds S declared tensors; tensor s is [G, per_s], so
+// model g owns [off_s + g*per_s, off_s + (g+1)*per_s). The segment
+// table is a device int64 [2, S] array: row 0 the offsets, row 1 the
+// per-model sizes.
+//
+// Layout: grid (chunks, G), 256 threads. Block (c, g) reads active[g]
+// once and returns as a whole when it is 0 (a block-uniform branch: no
+// load or store of a frozen model is ever issued). Otherwise the
+// `chunks` blocks of model g share the model's work units of 1024
+// elements (256 lanes x 4): segment s is ceil(per_s / 1024) units, the
+// units of all segments are numbered consecutively, and lane t < S of
+// a block reads segment t's table entry and counts the units before it
+// (walk_model_units: one round of table loads per block, S <= 256, no
+// per-element division or search). Inside a unit consecutive lanes sit
+// on consecutive addresses. A segment moves as 16-byte float4 (8-byte
+// bf16x4 for the mirror) when per_s % 4 == 0, its base off_s + g*per_s
+// is a multiple of 4 and every buffer is 16-byte aligned (the pad8
+// layout); it moves element-wise otherwise. The host sizes `chunks`
+// from n / G and S alone (it never reads the table), normally to one
+// unit per block. A table entry that does not fit into the buffer is
+// skipped, so a bad table cannot make the kernel touch memory outside
+// it.
+//
+// The per-element expressions repeat those of adam_kernel
+// (gordo_kernels.hip) and opt_kernel<KIND> (train_ops.hip), so an
+// active model's result is bit-equal to the unmasked step (see the
+// note at the RMSprop arm).
+
+#include <hip/hip_runtime.h>
+#include <hip/hip_bf16.h>
+#include <torch/extension.h>
+#include <ATen/cuda/CUDAContext.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+namespace {
+
+#define MK_DEV_INLINE __device__ __forceinline__
+
+using bf16 = __hip_bfloat16;
+
+// optimizer codes: 0 is plain Adam (adam_kernel), 1..5 those of
+// train_ops.hip
+constexpr int OPT_ADAM = 0, OPT_SGD = 1, OPT_RMSPROP = 2, OPT_ADAGRAD = 3,
+              OPT_ADAM_AMSGRAD = 4, OPT_ADAMAX = 5;
+
+struct OptConsts {
+  float h0, h1, h2, h3;  // plain Adam: lr, beta1, beta2, eps
+  float bc1, bc2;
+  int flag;
+};
+
+MK_DEV_INLINE bf16 f2bf(float v) { return __float2bfloat16(v); }
+
+// one element of the step: gi the gradient, pi the parameter, a/b/c the
+// state slots 0/1/2 (read and written only where the kind uses them)
+template <int KIND>
+MK_DEV_INLINE void opt_elem(const OptConsts& k, float gi, float& pi, float& a,
+                            float& b, float& c) {
+  const float h0 = k.h0, h1 = k.h1, h2 = k.h2, h3 = k.h3;
+  const float bc1 = k.bc1, bc2 = k.bc2;
+  if (KIND == OPT_ADAM) {
+    const float lr = h0, b1 = h1, b2 = h2, eps = h3;
+    float mi = b1 * a + (1.f - b1) * gi;
+    float vi = b2 * b + (1.f - b2) * gi * gi;
+    a = mi;
+    b = vi;
+    pi = pi - lr / bc1 * mi / (sqrtf(vi / bc2) + eps);
+  } else if (KIND == OPT_SGD) {
+    if (h1 == 0.f) {
+      pi -= h0 * gi;
+    } else {
+      float mi = h1 * a - h0 * gi;
+      a = mi;
+      pi += k.flag ? h1 * mi - h0 * gi : mi;
+    }
+  } else if (KIND == OPT_RMSPROP) {
+    // opt_kernel<OPT_RMSPROP> forms this sum from rounded products
+    // (its two multiplies pair up as one packed multiply, which leaves
+    // no multiply-add to fuse); fusing here would differ in the last
+    // bit, so contraction is off for this one statement
+    float vi;
+    {
+#pragma clang fp contract(off)
+      vi = h1 * a + (1.f - h1) * gi * gi;
+    }
+    a = vi;
+    float inc = h0 * gi / sqrtf(vi + h3);
+    if (h2 > 0.f) {
+      float mi = h2 * b + inc;
+      b = mi;
+      pi -= mi;
+    } else {
+      pi -= inc;
+    }
+  } else if (KIND == OPT_ADAGRAD) {
+    float ai = a + gi * gi;
+    a = ai;
+    pi -= h0 * gi / sqrtf(ai + h1);
+  } else if (KIND == OPT_ADAM_AMSGRAD) {
+    float mi = h1 * a + (1.f - h1) * gi;
+    float vi = h2 * b + (1.f - h2) * gi * gi;
+    float vh = fmaxf(c, vi);
+    a = mi;
+    b = vi;
+    c = vh;
+    pi -= h0 * sqrtf(bc2) / bc1 * mi / (sqrtf(vh) + h3);
+  } else {  // OPT_ADAMAX
+    float mi = h1 * a + (1.f - h1) * gi;
+    float ui = fmaxf(h2 * b, fabsf(gi));
+    a = mi;
+    b = ui;
+    pi -= h0 / bc1 * mi / (ui + h3);
+  }
+}
+
+MK_DEV_INLINE void store_bf16x4(bf16* dst, const float4& v) {
+  union {
+    bf16 h[4];
+    uint2 u;
+  } pk;
+  pk.h[0] = f2bf(v.x);
+  pk.h[1] = f2bf(v.y);
+  pk.h[2] = f2bf(v.z);
+  pk.h[3] = f2bf(v.w);
+  *reinterpret_cast<uint2*>(dst) = pk.u;
+}
+
+// the segment's slice of model g, or false when the table entry does
+// not fit into the n-element buffer
+MK_DEV_INLINE bool segment_slice(const long long* __restrict__ table, int S,
+                                 int s, int g, int G, size_t n,
+                                 size_t n_model, size_t& base, size_t& per) {
+  long long off = table[s];
+  long long len = table[S + s];
+  if (off < 0 || len <= 0) return false;
+  // n_model = n / G (from the host), so len * G cannot exceed n
+  if ((size_t)len > n_model || (size_t)off > n - (size_t)len * G)
+    return false;
+  base = (size_t)off + (size_t)g * (size_t)len;
+  per = (size_t)len;
+  return true;
+}
+
+// A block moves UNIT elements at a time: 256 lanes x 4 elements.
+constexpr int UNIT_SHIFT = 10;
+constexpr size_t UNIT = (size_t)1 << UNIT_SHIFT;
+// one lane per segment builds the unit table: S <= block size
+constexpr int MAX_SEGMENTS = 256;
+
+// Walks model g's work units for block blockIdx.x of gridDim.x (256
+// threads, all of them must call it). A segment of per_s elements is
+// ceil(per_s / UNIT) units, and the units of the S segments are
+// numbered one after the other. Lane t < S reads segment t's table
+// entry and counts the units before it (LDS, 4 arrays of S words); the
+// block then takes units blockIdx.x, blockIdx.x + gridDim.x, ...: the
+// one lane whose segment holds the unit names it, no division and no
+// search. For the unit's element range [lo, hi) of its segment it
+// calls, per lane, vec4(e) for 4 elements at flat index e where the
+// segment moves as 16-byte vectors, else one(e) per element with the
+// block's lanes on consecutive e.
+template <class FV, class FS>
+MK_DEV_INLINE void walk_model_units(const long long* __restrict__ table,
+                                    int S, int g, int G, size_t n,
+                                    size_t n_model, int vec_ok, FV&& vec4,
+                                    FS&& one) {
+  // lane t < S holds segment t: one round of table loads for the whole
+  // block instead of a chain of dependent scalar loads per segment
+  __shared__ size_t sh_base[MAX_SEGMENTS], sh_per[MAX_SEGMENTS];
+  __shared__ size_t sh_units[MAX_SEGMENTS], sh_first[MAX_SEGMENTS];
+  __shared__ size_t sh_total;
+  __shared__ int sh_seg;
+  const int t = threadIdx.x;
+  size_t my_units = 0;
+  if (t < S) {
+    size_t base = 0, per = 0;
+    if (segment_slice(table, S, t, g, G, n, n_model, base, per))
+      my_units = (per + UNIT - 1) >> UNIT_SHIFT;
+    sh_base[t] = base;
+    sh_per[t] = per;
+    sh_units[t] = my_units;
+  }
+  __syncthreads();
+  // number of segment t's first unit: the units of the segments before
+  size_t my_first = 0;
+  if (t < S) {
+    for (int j = 0; j < t; ++j) my_first += sh_units[j];
+    sh_first[t] = my_first;
+    if (t == S - 1) sh_total = my_first + my_units;
+  }
+  __syncthreads();
+  const size_t total = sh_total;
+  // the trip count depends on blockIdx and total alone: uniform
+  for (size_t u = blockIdx.x; u < total; u += gridDim.x) {
+    if (t < S && u >= my_first && u < my_first + my_units) sh_seg = t;
+    __syncthreads();
+    const int s = sh_seg;
+    const size_t base = sh_base[s], per = sh_per[s];
+    const size_t first = sh_first[s];
+    __syncthreads();  // sh_seg is read: the next round may write it
+    const size_t lo = (u - first) << UNIT_SHIFT;
+    const size_t hi = lo + UNIT < per ? lo + UNIT : per;
+    if (vec_ok && (per & 3) == 0 && (base & 3) == 0) {
+      const size_t i = lo + ((size_t)threadIdx.x << 2);
+      if (i < hi) vec4(base + i);  // hi % 4 == 0: the 4 are inside
+    } else {
+      for (size_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
+        one(base + i);
+    }
+  }
+}
+
+template <int KIND>
+__global__ void opt_masked_kernel(
+    float* __restrict__ p, const float* __restrict__ g,
+    float* __restrict__ s0, float* __restrict__ s1, float* __restrict__ s2,
+    bf16* __restrict__ plp, size_t n, float h0, float h1, float h2, float h3,
+    int flag, const int* __restrict__ step_buf,
+    const int* __restrict__ active, const long long* __restrict__ table,
+    int S, int vec_ok, size_t n_model) {
+  const int mg = blockIdx.y;
+  if (active[mg] == 0) return;
+  OptConsts k;
+  k.h0 = h0, k.h1 = h1, k.h2 = h2, k.h3 = h3;
+  k.bc1 = 1.f, k.bc2 = 1.f;
+  k.flag = flag;
+  if (KIND == OPT_ADAM) {
+    float fstep = (float)*step_buf;
+    k.bc1 = 1.f - __powf(h1, fstep);
+    k.bc2 = 1.f - __powf(h2, fstep);
+  } else if (KIND == OPT_ADAM_AMSGRAD || KIND == OPT_ADAMAX) {
+    float fstep = (float)*step_buf;
+    k.bc1 = 1.f - powf(h1, fstep);
+    k.bc2 = 1.f - powf(h2, fstep);
+  }
+  // which state slots this kind reads and writes (block-uniform)
+  const bool use0 = KIND != OPT_SGD || h1 != 0.f;
+  const bool use1 = KIND == OPT_ADAM || KIND == OPT_ADAM_AMSGRAD ||
+                    KIND == OPT_ADAMAX || (KIND == OPT_RMSPROP && h2 > 0.f);
+  const bool use2 = KIND == OPT_ADAM_AMSGRAD;
+  walk_model_units(
+      table, S, mg, (int)gridDim.y, n, n_model, vec_ok,
+      [&](size_t e) {
+        float4 gv = *reinterpret_cast<const float4*>(g + e);
+        float4 pv = *reinterpret_cast<const float4*>(p + e);
+        float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av, cv = av;
+        if (use0) av = *reinterpret_cast<const float4*>(s0 + e);
+        if (use1) bv = *reinterpret_cast<const float4*>(s1 + e);
+        if (use2) cv = *reinterpret_cast<const float4*>(s2 + e);
+        opt_elem<KIND>(k, gv.x, pv.x, av.x, bv.x, cv.x);
+        opt_elem<KIND>(k, gv.y, pv.y, av.y, bv.y, cv.y);
+        opt_elem<KIND>(k, gv.z, pv.z, av.z, bv.z, cv.z);
+        opt_elem<KIND>(k, gv.w, pv.w, av.w, bv.w, cv.w);
+        if (use0) *reinterpret_cast<float4*>(s0 + e) = av;
+        if (use1) *reinterpret_cast<float4*>(s1 + e) = bv;
+        if (use2) *reinterpret_cast<float4*>(s2 + e) = cv;
+        *reinterpret_cast<float4*>(p + e) = pv;
+        if (plp) store_bf16x4(plp + e, pv);
+      },
+      [&](size_t e) {
+        float gi = g[e];
+        float pi = p[e];
+        float a = 0.f, b = 0.f, c = 0.f;
+        if (use0) a = s0[e];
+        if (use1) b = s1[e];
+        if (use2) c = s2[e];
+        opt_elem<KIND>(k, gi, pi, a, b, c);
+        if (use0) s0[e] = a;
+        if (use1) s1[e] = b;
+        if (use2) s2[e] = c;
+        p[e] = pi;
+        if (plp) plp[e] = f2bf(pi);
+      });
+}
+
+__global__ void masked_copy_kernel(float* __restrict__ dst,
+                                   const float* __restrict__ src,
+                                   bf16* __restrict__ dlp, size_t n,
+                                   const int* __restrict__ mask,
+                                   const long long* __restrict__ table, int S,
+                                   int vec_ok, size_t n_model) {
+  const int mg = blockIdx.y;
+  if (mask[mg] == 0) return;
+  walk_model_units(
+      table, S, mg, (int)gridDim.y, n, n_model, vec_ok,
+      [&](size_t e) {
+        float4 v = *reinterpret_cast<const float4*>(src + e);
+        *reinterpret_cast<float4*>(dst + e) = v;
+        if (dlp) store_bf16x4(dlp + e, v);
+      },
+      [&](size_t e) {
+        float v = src[e];
+        dst[e] = v;
+        if (dlp) dlp[e] = f2bf(v);
+      });
+}
+
+// the step counter bump of the unmasked entries, launched the same way
+__global__ void masked_bump_kernel(int* step_buf) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *step_buf += 1;
+}
+
+hipStream_t cur_stream() {
+  return at::cuda::getCurrentCUDAStream().stream();
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// [G] int32 mask and [2, S] int64 table on p's device; returns (G, S)
+std::pair<int, int> check_mask_table(const torch::Tensor& p,
+                                     const torch::Tensor& mask,
+                                     const torch::Tensor& table) {
+  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kInt32 &&
+                  mask.is_contiguous() && mask.dim() == 1,
+              "the model mask must be a contiguous int32 [G] GPU tensor");
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == torch::kInt64 &&
+                  table.is_contiguous() && table.dim() == 2 &&
+                  table.size(0) == 2,
+              "the segment table must be a contiguous int64 [2, S] GPU "
+              "tensor");
+  TORCH_CHECK(mask.get_device() == p.get_device() &&
+                  table.get_device() == p.get_device(),
+              "mask and segment table must live on the buffer's device");
+  int64_t G = mask.numel(), S = table.size(1);
+  TORCH_CHECK(G >= 1 && G <= 65535, "G must be in [1, 65535]");
+  TORCH_CHECK(S >= 1 && S <= MAX_SEGMENTS, "the segment table holds ", S,
+              " tensors; the masked kernels take 1 to ", MAX_SEGMENTS);
+  return {(int)G, (int)S};
+}
+
+// blocks per model: one per work unit -- a model has at most
+// n/G/1024 + S units (each segment's last unit may be partial) --
+// capped so the grid stays near the unmasked entry's 4096 blocks
+int chunks_for(size_t n, int G, int S) {
+  size_t per_model = n / (size_t)G;
+  size_t want = (per_model >> UNIT_SHIFT) + (size_t)S;
+  size_t cap = std::max<size_t>(1, 4096 / (size_t)G);
+  return (int)std::max<size_t>(1, std::min(want, cap));
+}
+
+}  // namespace
+
+namespace gordo_masked {
+
+void optimizer_step_masked(int64_t kind, torch::Tensor p, torch::Tensor g,
+                           c10::optional<torch::Tensor> s0,
+                           c10::optional<torch::Tensor> s1,
+                           c10::optional<torch::Tensor> s2,
+                           std::vector<double> hyper, bool flag,
+                           c10::optional<torch::Tensor> plp,
+                           torch::Tensor step_buf, torch::Tensor active,
+                           torch::Tensor table) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
+                  p.is_contiguous(),
+              "p must be a contiguous fp32 GPU tensor");
+  TORCH_CHECK(g.is_cuda() && g.scalar_type() == torch::kFloat32 &&
+                  g.is_contiguous() && g.numel() == p.numel(),
+              "g must match p");
+  TORCH_CHECK(step_buf.is_cuda() && step_buf.scalar_type() == torch::kInt32,
+              "step_buf must be an int32 GPU tensor");
+  TORCH_CHECK(hyper.size() == 4, "hyper must hold 4 values");
+  auto gs = check_mask_table(p, active, table);
+  int G = gs.first, S = gs.second;
+  size_t n = p.numel();
+  bool vec = aligned16(p.data_ptr()) && aligned16(g.data_ptr());
+  auto slot = [&](const c10::optional<torch::Tensor>& s, bool needed,
+                  const char* name) -> float* {
+    if (!needed) return nullptr;
+    TORCH_CHECK(s.has_value(), name, " is required for this optimizer");
+    TORCH_CHECK(s->is_cuda() && s->scalar_type() == torch::kFloat32 &&
+                    s->is_contiguous() && (size_t)s->numel() == n,
+                name, " must match p");
+    vec = vec && aligned16(s->data_ptr());
+    return s->data_ptr<float>();
+  };
+  bf16* plp_ptr = nullptr;
+  if (plp.has_value()) {
+    TORCH_CHECK(plp->is_cuda() && plp->scalar_type() == torch::kBFloat16 &&
+                    plp->is_contiguous() && (size_t)plp->numel() == n,
+                "p_lp must be a bf16 mirror of p");
+    plp_ptr = (bf16*)plp->data_ptr();
+    vec = vec && aligned16(plp_ptr);
+  }
+  float h0 = (float)hyper[0], h1 = (float)hyper[1], h2 = (float)hyper[2],
+        h3 = (float)hyper[3];
+  float *a = nullptr, *b = nullptr, *c = nullptr;
+  switch (kind) {
+    case OPT_ADAM:
+      a = slot(s0, true, "s0");
+      b = slot(s1, true, "s1");
+      break;
+    case OPT_SGD:
+      a = slot(s0, h1 != 0.f, "s0");
+      break;
+    case OPT_RMSPROP:
+      a = slot(s0, true, "s0");
+      b = slot(s1, h2 > 0.f, "s1");
+      break;
+    case OPT_ADAGRAD:
+      a = slot(s0, true, "s0");
+      break;
+    case OPT_ADAM_AMSGRAD:
+      a = slot(s0, true, "s0");
+      b = slot(s1, true, "s1");
+      c = slot(s2, true, "s2");
+      break;
+    case OPT_ADAMAX:
+      a = slot(s0, true, "s0");
+      b = slot(s1, true, "s1");
+      break;
+    default:
+      TORCH_CHECK(false, "bad optimizer code ", kind);
+  }
+  hipLaunchKernelGGL(masked_bump_kernel, dim3(1), dim3(64), 0, cur_stream(),
+                     step_buf.data_ptr<int>());
+  if (n == 0) return;
+  TORCH_CHECK(n % (size_t)G == 0, "buffer size must be a multiple of G");
+  int chunks = chunks_for(n, G, S);
+#define GORDO_MASKED_LAUNCH(K)                                               \
+  hipLaunchKernelGGL(opt_masked_kernel<K>, dim3(chunks, G), dim3(256), 0,    \
+                     cur_stream(), p.data_ptr<float>(), g.data_ptr<float>(), \
+                     a, b, c, plp_ptr, n, h0, h1, h2, h3, flag ? 1 : 0,      \
+                     step_buf.data_ptr<int>(), active.data_ptr<int>(),       \
+                     (const long long*)table.data_ptr<int64_t>(), S,         \
+                     vec ? 1 : 0, n / (size_t)G)
+  switch (kind) {
+    case OPT_ADAM: GORDO_MASKED_LAUNCH(OPT_ADAM); break;
+    case OPT_SGD: GORDO_MASKED_LAUNCH(OPT_SGD); break;
+    case OPT_RMSPROP: GORDO_MASKED_LAUNCH(OPT_RMSPROP); break;
+    case OPT_ADAGRAD: GORDO_MASKED_LAUNCH(OPT_ADAGRAD); break;
+    case OPT_ADAM_AMSGRAD: GORDO_MASKED_LAUNCH(OPT_ADAM_AMSGRAD); break;
+    default: GORDO_MASKED_LAUNCH(OPT_ADAMAX); break;
+  }
+#undef GORDO_MASKED_LAUNCH
+}
+
+void masked_copy(torch::Tensor dst, torch::Tensor src, torch::Tensor mask,
+                 torch::Tensor table, c10::optional<torch::Tensor> dst_lp) {
+  TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == torch::kFloat32 &&
+                  dst.is_contiguous(),
+              "dst must be a contiguous fp32 GPU tensor");
+  TORCH_CHECK(src.is_cuda() && src.scalar_type() == torch::kFloat32 &&
+                  src.is_contiguous() && src.numel() == dst.numel() &&
+                  src.get_device() == dst.get_device(),
+              "src must match dst");
+  auto gs = check_mask_table(dst, mask, table);
+  int G = gs.first, S = gs.second;
+  size_t n = dst.numel();
+  bool vec = aligned16(dst.data_ptr()) && aligned16(src.data_ptr());
+  bf16* lp_ptr = nullptr;
+  if (dst_lp.has_value()) {
+    TORCH_CHECK(dst_lp->is_cuda() &&
+                    dst_lp->scalar_type() == torch::kBFloat16 &&
+                    dst_lp->is_contiguous() && (size_t)dst_lp->numel() == n,
+                "dst_lp must be a bf16 mirror of dst");
+    lp_ptr = (bf16*)dst_lp->data_ptr();
+    vec = vec && aligned16(lp_ptr);
+  }
+  if (n == 0) return;
+  TORCH_CHECK(n % (size_t)G == 0, "buffer size must be a multiple of G");
+  int chunks = chunks_for(n, G, S);
+  hipLaunchKernelGGL(masked_copy_kernel, dim3(chunks, G), dim3(256), 0,
+                     cur_stream(), dst.data_ptr<float>(),
+                     src.data_ptr<float>(), lp_ptr, n, mask.data_ptr<int>(),
+                     (const long long*)table.data_ptr<int64_t>(), S,
+                     vec ? 1 : 0, n / (size_t)G);
+}
+
+}  // namespace gordo_masked

@@ -281,6 +281,74 @@ def adam_step(
         p_lp.copy_(p)
 
 
+def segment_table(offsets, sizes, device=None) -> torch.Tensor:
+    """The int64 [2, S] segment table of a flat buffer of S tensors:
+    tensor s is [G, sizes[s]] and starts at offsets[s], so model g owns
+    [offsets[s] + g*sizes[s], offsets[s] + (g+1)*sizes[s])."""
+    return torch.tensor(
+        [[int(o) for o in offsets], [int(n) for n in sizes]],
+        dtype=torch.int64, device=device,
+    ).reshape(2, -1)
+
+
+def _model_slices(t: torch.Tensor, mask: torch.Tensor, table: torch.Tensor):
+    """(rows, [G, per_s] view of t) per segment, rows the masked models."""
+    rows = torch.nonzero(mask.reshape(-1) != 0).reshape(-1)
+    G = mask.numel()
+    for off, per in zip(*table.tolist()):
+        yield rows, t[off : off + G * per].view(G, per)
+
+
+def masked_copy(
+    dst: torch.Tensor,
+    src: torch.Tensor,
+    mask: torch.Tensor,
+    table: torch.Tensor,
+    dst_lp: Optional[torch.Tensor] = None,
+):
+    """dst <- src for the slices of the models with ``mask[g] != 0``
+    (``table``: see ``segment_table``); ``dst_lp``, when given, gets the
+    same slices in its own precision. Everything else stays as it is."""
+    for (rows, d), (_, s) in zip(
+        _model_slices(dst, mask, table), _model_slices(src, mask, table)
+    ):
+        d[rows] = s[rows]
+    if dst_lp is not None:
+        for (rows, d), (_, s) in zip(
+            _model_slices(dst_lp, mask, table), _model_slices(src, mask, table)
+        ):
+            d[rows] = s[rows].to(dst_lp.dtype)
+
+
+def optimizer_step_masked(
+    kind: str,
+    p: torch.Tensor,
+    g: torch.Tensor,
+    s0: Optional[torch.Tensor],
+    s1: Optional[torch.Tensor],
+    s2: Optional[torch.Tensor],
+    hyper: dict,
+    step: int,
+    p_lp: Optional[torch.Tensor],
+    active: torch.Tensor,
+    table: torch.Tensor,
+):
+    """``optimizer_step`` for the models with ``active[g] != 0`` only:
+    the parameters, state slots and mirror of every other model keep
+    their bits, whatever its gradient holds. The step runs over the
+    whole buffer, so an active element sees exactly the arithmetic of
+    the unmasked step, and the frozen slices are put back afterwards."""
+    frozen = (active.reshape(-1) == 0).to(torch.int32)
+    bufs = [t for t in (p, s0, s1, s2, p_lp) if t is not None]
+    saved = [t.clone() for t in bufs] if bool(frozen.any()) else []
+    optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp)
+    for t, keep in zip(bufs, saved):
+        for (rows, d), (_, s) in zip(
+            _model_slices(t, frozen, table), _model_slices(keep, frozen, table)
+        ):
+            d[rows] = s[rows]
+
+
 def lstm_pointwise_fwd(
     gates: torch.Tensor, c_prev: torch.Tensor, act="tanh"
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -563,9 +563,13 @@ class PackedFleetBuilder:
                            cv_duration=cv_duration, spec=spec):
             t0 = time.time()
             all_states = pack.states_for_all_models()
+            # each machine keeps the epochs it ran itself (per-model
+            # early stopping), not those of its slowest pack neighbour
+            epochs_run = getattr(history, "epochs_run", None)
             for g_idx, p in enumerate(group):
+                n_ep = None if epochs_run is None else int(epochs_run[g_idx])
                 hist = {
-                    k: [float(ep[g_idx]) for ep in v]
+                    k: [float(ep[g_idx]) for ep in v[:n_ep]]
                     for k, v in history.items()
                 }
                 p.keras_est.adopt_pack_result(
@@ -1190,8 +1194,8 @@ def _engine_fit_args(fit_args: Dict[str, Any]) -> Dict[str, Any]:
             out[k] = fit_args[k]
     if fit_args.get("validation_split"):
         out["validation_split"] = float(fit_args["validation_split"])
-    # identical callbacks are part of the group key (fit_args), so the
-    # lockstep all-models-stalled semantics of pack.fit applies per group
+    # identical callbacks are part of the group key (fit_args); pack.fit
+    # stops each model of the group at its own patience
     es = _parse_early_stopping(fit_args.get("callbacks"))
     if es is not None:
         out["early_stopping"] = es
