@@ -256,12 +256,64 @@ class DiffBasedAnomalyDetector(AnomalyDetectorBase):
         serving."""
         self._serve_device = device
 
-    def _fused_device_scores(self, data: pd.DataFrame, y: pd.DataFrame):
+    # largest smm window of ops.smooth (its LDS-resident sorted window)
+    _DEVICE_SMOOTH_MAX_SMM_WINDOW = 8192
+
+    def _device_smooth_wanted(self, n_rows: int) -> bool:
+        """Whether anomaly() should smooth on the device: a window and a
+        known method, enough rows for the device scoring path, smm
+        within the kernel's window limit, and ``GORDO_DEVICE_SMOOTH``
+        (read per call) not "0"."""
+        import os
+
+        return (
+            self.window is not None
+            and self.smoothing_method in ("smm", "sma", "ewma")
+            and n_rows >= self._DEVICE_SCORE_MIN_ROWS
+            and os.environ.get("GORDO_DEVICE_SMOOTH") != "0"
+            and (
+                self.smoothing_method != "smm"
+                or self.window <= self._DEVICE_SMOOTH_MAX_SMM_WINDOW
+            )
+        )
+
+    def _device_smooth_families(self, resident):
+        """The four smooth-* families from the device-resident raw
+        scores (ts [n, F], tots [n], tu [n, F], totu [n]): one
+        [2F+2, n] matrix, one ops.smooth launch, one D2H copy. Returns
+        fp64 numpy (tag_scaled [n, F], total_scaled [n], tag_unscaled
+        [n, F], total_unscaled [n]), or None to smooth with pandas."""
+        try:
+            import torch
+
+            from .... import ops
+
+            ts, tots, tu, totu = resident
+            F = ts.shape[1]
+            stacked = torch.cat(
+                [ts.t(), tots.unsqueeze(0), tu.t(), totu.unsqueeze(0)]
+            )
+            sm = ops.smooth(
+                stacked, int(self.window), self.smoothing_method
+            ).cpu().numpy()
+            return (
+                sm[:F].T,
+                sm[F],
+                sm[F + 1:2 * F + 1].T,
+                sm[2 * F + 1],
+            )
+        except Exception:  # any wobble → exact pandas smoothing
+            logger.debug("device smoothing unavailable", exc_info=True)
+            return None
+
+    def _fused_device_scores(self, data: pd.DataFrame, y: pd.DataFrame,
+                             resident: Optional[list] = None):
         """Serving hot path: one fused HIP kernel (ops.anomaly_score,
         kernel K9) computes every residual column family when a GPU is
         present and the scaler is a fitted MinMaxScaler-style affine
         transform. Returns (tag_scaled, total_scaled, tag_unscaled,
-        total_unscaled) as numpy, or None to use the pandas path."""
+        total_unscaled) as numpy, or None to use the pandas path. A
+        ``resident`` list receives the same four as device tensors."""
         try:
             import torch
 
@@ -297,6 +349,8 @@ class DiffBasedAnomalyDetector(AnomalyDetectorBase):
             ts, tots, tu, totu, _, _ = ops.anomaly_score(
                 out, yt, scale, minv, None, 1.0
             )
+            if resident is not None:
+                resident.extend((ts, tots, tu, totu))
             return (
                 ts.cpu().numpy(),
                 tots.cpu().numpy(),
@@ -329,7 +383,13 @@ class DiffBasedAnomalyDetector(AnomalyDetectorBase):
             frequency=frequency,
         )
 
-        scored = self._fused_device_scores(data, y)
+        # device smoothing keeps the raw scores resident for one more
+        # launch; otherwise the scoring call is the plain one
+        resident = [] if self._device_smooth_wanted(len(data)) else None
+        if resident is not None:
+            scored = self._fused_device_scores(data, y, resident)
+        else:
+            scored = self._fused_device_scores(data, y)
         if scored is not None:
             ts, tots, tu, totu = scored
         else:
@@ -376,7 +436,18 @@ class DiffBasedAnomalyDetector(AnomalyDetectorBase):
             fam1("total-anomaly-unscaled", totu),
         ]
 
-        if self.window is not None and self.smoothing_method is not None:
+        smoothed = (
+            self._device_smooth_families(resident) if resident else None
+        )
+        if smoothed is not None:
+            # same names, order, index and float64 dtype as the pandas
+            # branch below
+            sm_ts, sm_tots, sm_tu, sm_totu = smoothed
+            blocks.append(fam("smooth-tag-anomaly-scaled", sm_ts))
+            blocks.append(fam1("smooth-total-anomaly-scaled", sm_tots))
+            blocks.append(fam("smooth-tag-anomaly-unscaled", sm_tu))
+            blocks.append(fam1("smooth-total-anomaly-unscaled", sm_totu))
+        elif self.window is not None and self.smoothing_method is not None:
             smooth_tag_anomaly_scaled = self._smoothing(tag_anomaly_scaled)
             smooth_tag_anomaly_scaled.columns = (
                 smooth_tag_anomaly_scaled.columns.set_levels(
@@ -542,11 +613,12 @@ class DiffBasedKFCVAnomalyDetector(DiffBasedAnomalyDetector):
         )
 
     def _device_threshold(self, validation_metric):
-        """K11+K12 device path: rolling(window).median() then
-        NaN-dropping quantile, both as HIP kernels when a GPU is
-        present and the smoothing is the default smm. Matches the
-        pandas pipeline at fp32 (min_periods=window NaN semantics in
-        the windowed kernel; linear interpolation in both). Returns a
+        """K11+K12 device path: the smoothing, then the NaN-dropping
+        quantile, both as HIP kernels when a GPU is present. smm is
+        rolling(window).median() through ops.windowed_quantile; sma and
+        ewma go through ops.smooth and its fp32 cast. Matches the
+        pandas pipeline at fp32 (min_periods=window NaN semantics for
+        smm and sma; linear interpolation in the quantiles). Returns a
         Series for DataFrame input, a float for Series input, or None
         to take the pandas path."""
         try:
@@ -555,7 +627,7 @@ class DiffBasedKFCVAnomalyDetector(DiffBasedAnomalyDetector):
             from .... import ops
 
             if (
-                self.smoothing_method != "smm"
+                self.smoothing_method not in ("smm", "sma", "ewma")
                 or not torch.cuda.is_available()
                 or not ops.hip_available()
                 or len(validation_metric) < max(self.window, 64)
@@ -566,7 +638,12 @@ class DiffBasedKFCVAnomalyDetector(DiffBasedAnomalyDetector):
             cols = arr.reshape(len(arr), -1).T  # [R, N]
             dev = torch.as_tensor(np.ascontiguousarray(cols),
                                   device="cuda")
-            sm = ops.windowed_quantile(dev, int(self.window), 0.5)
+            if self.smoothing_method == "smm":
+                sm = ops.windowed_quantile(dev, int(self.window), 0.5)
+            else:
+                sm = ops.smooth(
+                    dev, int(self.window), self.smoothing_method
+                ).to(torch.float32)
             q = ops.row_quantile(sm, float(self.threshold_percentile))
             out = q.cpu().numpy().astype(np.float64)
             if isinstance(validation_metric, pd.DataFrame):

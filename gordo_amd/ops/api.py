@@ -559,6 +559,54 @@ def row_quantile(X, q: float):
     )
 
 
+_SMOOTH_METHODS = {"smm": 0, "sma": 1, "ewma": 2}
+
+
+def smooth(X, window: int, method: str):
+    """Per-row smoothing of ``X`` [R, N] with pandas semantics, fp64
+    [R, N] out (completes K11): ``"smm"`` is ``rolling(window)
+    .median()``, ``"sma"`` ``rolling(window).mean()`` and ``"ewma"``
+    ``ewm(span=window).mean()``. NaN and +-inf are missing values in
+    all three. GPU tensors run the HIP kernels (csrc/smoothing.hip;
+    ``window >= 1``, smm ``window <= 8192``); CPU tensors take the
+    pandas expressions of ``DiffBasedAnomalyDetector._smoothing``."""
+    if method not in _SMOOTH_METHODS:
+        raise ValueError(
+            f"Unknown smoothing method {method!r}: expected one of "
+            f"{sorted(_SMOOTH_METHODS)}"
+        )
+    window = int(window)
+    if _on_gpu(X):
+        return _require_hip().smooth(X, window, _SMOOTH_METHODS[method])
+    if window < 1:
+        raise ValueError("window must be at least 1")
+    import pandas as _pd
+
+    df = _pd.DataFrame(X.numpy().T)
+    if method == "smm":
+        sm = df.rolling(window).median()
+    elif method == "sma":
+        sm = df.rolling(window).mean()
+    else:
+        sm = df.ewm(span=window).mean()
+    import numpy as _np
+
+    return torch.as_tensor(
+        _np.ascontiguousarray(sm.to_numpy(dtype=_np.float64).T)
+    )
+
+
+def last_smooth_launch() -> dict:
+    """What this thread's last GPU ``smooth`` call launched:
+    ``method`` (smm/sma/ewma), ``family`` ("smm_slide", "sma_window",
+    "ewma_scan"; "nan_fill" when ``window > n`` left nothing to launch
+    for smm/sma, "empty" for an empty input), ``rows``, ``n`` and
+    ``window``. Host-side record; ``family`` is "" before any call."""
+    method, family, rows, n, window = _require_hip().last_smooth_launch()
+    return {"method": method, "family": family, "rows": rows, "n": n,
+            "window": window}
+
+
 def lstm_pointwise_fwd(gates, c_prev, act="tanh"):
     act = act_code(act)
     if _on_gpu(gates):

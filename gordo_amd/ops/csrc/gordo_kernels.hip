@@ -996,6 +996,14 @@ torch::Tensor windowed_quantile(torch::Tensor X, int64_t w, double q);
 torch::Tensor row_quantile(torch::Tensor X, double q);
 }  // namespace gordo_thresholds
 
+// device smoothing: smm / sma / ewma with pandas semantics
+// (smoothing.hip: completes K11)
+namespace gordo_smoothing {
+torch::Tensor smooth(torch::Tensor X, int64_t w, int64_t method);
+std::tuple<std::string, std::string, int64_t, int64_t, int64_t>
+last_smooth_launch();
+}  // namespace gordo_smoothing
+
 // configurable loss / optimizer train-step ops (train_ops.hip)
 namespace gordo_train {
 std::vector<torch::Tensor> loss_bwd(torch::Tensor Y, torch::Tensor T,
@@ -1046,6 +1054,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "(K11)");
   mod.def("row_quantile", &gordo_thresholds::row_quantile,
           "NaN-dropping linear-interpolated quantile per row (K12)");
+  mod.def("smooth", &gordo_smoothing::smooth,
+          "rolling median / rolling mean / ewm mean per row, fp64 [R, N] "
+          "(method 0 smm, 1 sma, 2 ewma; K11)");
+  mod.def("last_smooth_launch", &gordo_smoothing::last_smooth_launch,
+          "(method, family, rows, n, window) of this thread's last "
+          "smooth call");
   mod.def("anomaly_score", &gordo_anomaly::anomaly_score,
           "fused DiffBased anomaly scoring (serving hot path)");
   // trailing `act`: the LSTM cell activation code, tanh by default

@@ -633,6 +633,79 @@ def row_quantile_ref(X, q: float, return_neighbours=False):
 
 
 # ---------------------------------------------------------------------------
+# Smoothing (csrc/smoothing.hip: smm, sma, ewma). fp64 oracle written
+# from the definitions; no pandas rolling or ewm, so
+# tests/test_smoothing_oracle.py can validate it against them. NaN and
+# +-inf are missing values in all three methods.
+# ---------------------------------------------------------------------------
+SMOOTH_METHODS = ("smm", "sma", "ewma")
+
+
+def _smooth_one(X, w: int, method: str):
+    import numpy as np
+
+    R, N = X.shape
+    valid = np.isfinite(X)
+    out = np.full((R, N), np.nan)
+    if method == "ewma":
+        # num and den decay by d = 1 - alpha at every position; a valid
+        # value adds x and 1; a missing position repeats the last output
+        d = 1.0 - 2.0 / (w + 1.0)
+        num = np.zeros(R)
+        den = np.zeros(R)
+        last = np.full(R, np.nan)
+        for t in range(N):
+            v = valid[:, t]
+            num = num * d + np.where(v, X[:, t], 0.0)
+            den = den * d + np.where(v, 1.0, 0.0)
+            last = np.where(v, num / np.where(v, den, 1.0), last)
+            out[:, t] = last
+        return out
+    no = N - w + 1
+    if no <= 0:
+        return out  # no full window
+    bad = np.zeros((R, no), dtype=np.int64)  # missing values per window
+    for k in range(w):
+        bad += ~valid[:, k:k + no]
+    if method == "sma":
+        # each window's own values, added in ascending time order
+        acc = np.zeros((R, no))
+        clean = np.where(valid, X, 0.0)
+        for k in range(w):
+            acc = acc + clean[:, k:k + no]
+        res = acc / float(w)
+    else:
+        res = np.empty((R, no))
+        for r in range(R):
+            for i0 in range(no):
+                if bad[r, i0]:
+                    res[r, i0] = np.nan
+                    continue
+                s = np.sort(X[r, i0:i0 + w])
+                res[r, i0] = (s[(w - 1) // 2] + s[w // 2]) / 2.0
+    out[:, w - 1:] = np.where(bad > 0, np.nan, res)
+    return out
+
+
+def smooth_ref(X, w: int, method: str):
+    """``smooth`` oracle: per row of X [R, N] the rolling median (smm,
+    ``min_periods = w``), the rolling mean (sma, same) or the span-``w``
+    exponentially weighted mean (ewma, ``adjust=True``,
+    ``ignore_na=False``) in fp64, full [R, N] output. Returns
+    ``(value, value_abs)``: the statistic of x and the same statistic of
+    ``|x|``, which the tests scale their bounds by."""
+    import numpy as np
+
+    if method not in SMOOTH_METHODS:
+        raise ValueError(f"Unknown smoothing method {method!r}")
+    w = int(w)
+    if w < 1:
+        raise ValueError("window must be at least 1")
+    X = _as_f64_rows(X)
+    return _smooth_one(X, w, method), _smooth_one(np.abs(X), w, method)
+
+
+# ---------------------------------------------------------------------------
 # Grouped GEMM and pointwise training ops: fp64 oracles written from
 # the definitions (explicit sums over the contracted index, no bmm), so
 # tests/test_gemm_oracle.py can validate them against torch.bmm and
