@@ -65,6 +65,8 @@ def per_model_stopping():
     )
     print(f"pack ran {len(hist['loss'])} epochs; per model: "
           f"{hist.epochs_run}, best epochs {hist.best_epoch}")
+    # (epoch, G_before, G_after) per compaction; a pack of 2 never compacts
+    print(f"compactions: {hist.compactions}")
     for g in range(2):
         assert len(_history_for_model(hist, g)["loss"]) == hist.epochs_run[g]
 

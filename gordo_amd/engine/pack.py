@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .compaction import ratio_from_env, should_compact
 from .early_stop import EarlyStopState
 from .spec import ModelSpec
 
@@ -42,13 +43,19 @@ class FitHistory(dict):
     ``{key: [[G values] per epoch]}`` dict, plus ``epochs_run``, the
     number of epochs each model itself trained for (its stopped epoch
     + 1 under early stopping, else the epochs of the fit). Rows past
-    ``epochs_run[g]`` hold model g's frozen-weight values.
+    ``epochs_run[g]`` hold model g's frozen-weight values while model g
+    still rides along in the pack, and NaN once the pack has been
+    compacted to its live models; every consumer cuts them off.
     ``best_epoch`` (early stopping only) is each model's epoch of the
     best monitored value: the one ``restore_best_weights`` goes back
-    to."""
+    to. ``compactions`` (early stopping only; ``[]`` when none
+    happened) lists ``(epoch, G_before, G_after)`` for every time the
+    fit went on in a smaller pack of its live models, ``epoch`` the
+    0-based epoch after which it did."""
 
     epochs_run: Optional[List[int]] = None
     best_epoch: Optional[List[int]] = None
+    compactions: Optional[List[Tuple[int, int, int]]] = None
 
 
 def _compute_dtype(device: torch.device) -> torch.dtype:
@@ -212,6 +219,69 @@ class _ParamStore:
             dst, src, self.model_mask(mask), self.segments,
             self.plp if mirror else None,
         )
+
+    # -- pack compaction: whole models between stores of different G --
+    @property
+    def n_models(self) -> int:
+        return int(self._shapes[0][1][0])
+
+    def segments_for(self, G: int) -> torch.Tensor:
+        """Segment table of this store's tensors laid out for G models
+        (the flat buffer is the declared tensors one after the other,
+        so tensor s starts at sum_{k<s} G * per_k)."""
+        per = [
+            self._offsets[name][1] // self.n_models
+            for name, _ in self._shapes
+        ]
+        offsets = np.concatenate(([0], np.cumsum(per)[:-1])) * int(G)
+        return ops.segment_table(offsets.tolist(), per, self.device)
+
+    def gathered_p32(self, live) -> torch.Tensor:
+        """A new flat parameter buffer that holds this store's models
+        ``live``, in that order, laid out for ``len(live)`` models."""
+        live = [int(g) for g in live]
+        out = torch.empty(
+            self._total // self.n_models * len(live),
+            dtype=torch.float32, device=self.device,
+        )
+        ops.remap_models(
+            out, self.p32, list(range(len(live))), live,
+            self.segments_for(len(live)), self.segments,
+            len(live), self.n_models,
+        )
+        return out
+
+    def _move_models(self, dst: "_ParamStore", dst_index, src_index,
+                     extra=None) -> None:
+        """Models ``src_index`` of this store become models
+        ``dst_index`` of ``dst``: parameters (and dst's bf16 mirror, in
+        the same launch), every optimizer slot and, as ``extra = (dst
+        buffer, src buffer)``, one more buffer of the same layout. The
+        step counter carries over: every model that moves took every
+        step, which is also why the masked step shares one counter."""
+        args = (dst_index, src_index, dst.segments, self.segments,
+                dst.n_models, self.n_models)
+        ops.remap_models(dst.p32, self.p32, *args, dst_lp=dst.plp)
+        for (_k, d), (_k2, s) in zip(dst.slots(), self.slots()):
+            ops.remap_models(d, s, *args)
+        if extra is not None:
+            ops.remap_models(extra[0], extra[1], *args)
+        dst.step_count = self.step_count
+        if dst.step_buf is not None:
+            dst.step_buf.copy_(self.step_buf)
+
+    def gather_models(self, child: "_ParamStore", live, extra=None) -> None:
+        """``child``'s models 0, 1, ... <- this store's models ``live``
+        (``extra``: (child's buffer, this store's))."""
+        live = [int(g) for g in live]
+        self._move_models(child, list(range(len(live))), live, extra)
+
+    def scatter_models(self, child: "_ParamStore", live, extra=None) -> None:
+        """This store's models ``live`` <- ``child``'s models 0, 1, ...
+        (``extra``: (this store's buffer, child's)); the other models
+        of this store keep their bits."""
+        live = [int(g) for g in live]
+        child._move_models(self, live, list(range(len(live))), extra)
 
     def sync_lp(self):
         if self.plp is not None:
@@ -635,17 +705,23 @@ class BasePack:
         # model stops at its OWN patience. A stopped model still runs
         # forward and backward in lockstep with the pack, but the masked
         # optimizer step leaves its parameters, optimizer state and
-        # mirror alone, so its weights are those of a solo fit. The fit
-        # ends when every model has ended.
+        # mirror alone, so its weights are those of a solo fit. Once
+        # few enough models are left (engine/compaction.py) the fit
+        # goes on in a child pack of the live models only, which is
+        # scattered back into this one. The fit ends when every model
+        # has ended.
         es: Optional[EarlyStopState] = None
+        compact_ratio: Optional[float] = None
         if early_stopping is not None:
             es = EarlyStopState(G, early_stopping)
+            compact_ratio = ratio_from_env()
+            history.compactions = []
             if G > 1:
                 self.store.set_active(np.ones(G, dtype=bool))
         try:
             epochs_done = self._fit_epochs(
                 X, Y, epochs, batch_size, shuffle, verbose, history,
-                n_train, n_all, es,
+                n_train, n_all, es, compact_ratio,
             )
         finally:
             self.store.set_active(None)
@@ -660,99 +736,215 @@ class BasePack:
         return history
 
     def _fit_epochs(self, X, Y, epochs, batch_size, shuffle, verbose,
-                    history, n_train, n_all, es) -> int:
-        """The epoch loop of ``fit``; returns the number of epochs run."""
+                    history, n_train, n_all, es,
+                    compact_ratio: Optional[float] = None) -> int:
+        """The epoch loop of ``fit``; returns the number of epochs run.
+
+        ``cur`` is the pack that trains: this one, or, after a
+        compaction, a child pack whose model j is this pack's model
+        ``live[j]``. Early-stopping state, history rows and the shuffle
+        generators stay indexed by this pack's models."""
         G = X.shape[0]
         n_val = n_all - n_train
-        best_p32: Optional[torch.Tensor] = None
         n_batches = max(1, math.ceil(n_train / batch_size))
+        # one generator per model of THIS pack: a live model's stream
+        # goes on across a compaction
         gens = [torch.Generator().manual_seed(int(s) & 0x7FFFFFFF) for s in self.seeds]
+        cur: BasePack = self
+        live = np.arange(G)
+        Xc, Yc = X, Y  # cur's rows of the padded series
+        # best weights: best_p32 in this pack's layout, cur_best in
+        # cur's (the same buffer while cur is this pack)
+        best_p32: Optional[torch.Tensor] = None
+        cur_best: Optional[torch.Tensor] = None
         epochs_done = 0
-        for epoch in range(epochs):
-            epochs_done = epoch + 1
-            if shuffle:
-                perm = torch.stack(
-                    [torch.randperm(n_train, generator=g) for g in gens]
-                ).to(self.device)
-            else:
-                perm = (
-                    torch.arange(n_train, device=self.device)
-                    .unsqueeze(0)
-                    .expand(G, -1)
-                )
-            epoch_loss = torch.zeros(G, dtype=torch.float32, device=self.device)
-            epoch_correct = torch.zeros(
-                G, dtype=torch.float32, device=self.device
-            )
-            samples_seen = 0
-            for b in range(n_batches):
-                idx = perm[:, b * batch_size : (b + 1) * batch_size]
-                if idx.shape[1] == 0:
-                    continue
-                Xb, Tb = self._gather_batch(X, Y, idx)
-                loss = self._graph_train_step(Xb, Tb)
-                if loss is None:
-                    loss = self.train_batch(Xb, Tb)
-                epoch_loss += loss * idx.shape[1]
-                epoch_correct += self.last_correct
-                samples_seen += idx.shape[1]
-            # loss and accuracy leave the device together: one transfer
-            epoch_stats = torch.stack(
-                [epoch_loss, epoch_correct]
-            ) / max(samples_seen, 1)
-            epoch_loss, epoch_acc = epoch_stats.cpu().tolist()
-            history["loss"].append(epoch_loss)
-            history["accuracy"].append(epoch_acc)
-            if n_val > 0:
-                val_loss = torch.zeros(G, dtype=torch.float32, device=self.device)
-                val_correct = torch.zeros(
-                    G, dtype=torch.float32, device=self.device
-                )
-                vseen = 0
-                for vs_ in range(n_train, n_all, batch_size):
-                    vidx = (
-                        torch.arange(
-                            vs_, min(vs_ + batch_size, n_all), device=self.device
-                        ).unsqueeze(0).expand(G, -1)
+
+        def row(values):
+            """A [G] history row from cur's per-model values."""
+            if cur is self:
+                return values
+            out = [math.nan] * G
+            for j, g in enumerate(live):
+                out[g] = values[j]
+            return out
+
+        try:
+            for epoch in range(epochs):
+                epochs_done = epoch + 1
+                Gc = cur.G
+                if shuffle:
+                    perm = torch.stack(
+                        [torch.randperm(n_train, generator=gens[g])
+                         for g in live]
+                    ).to(self.device)
+                else:
+                    perm = (
+                        torch.arange(n_train, device=self.device)
+                        .unsqueeze(0)
+                        .expand(Gc, -1)
                     )
-                    Xvb, Tvb = self._gather_batch(X, Y, vidx)
-                    vl, vc = self.eval_batch_stats(Xvb, Tvb)
-                    val_loss += vl * vidx.shape[1]
-                    val_correct += vc
-                    vseen += vidx.shape[1]
-                val_losses, val_acc = (
-                    torch.stack([val_loss, val_correct]) / max(vseen, 1)
-                ).cpu().tolist()
-                history["val_loss"].append(val_losses)
-                history["val_accuracy"].append(val_acc)
-            if verbose:
-                logger.info(
-                    "epoch %d/%d mean-loss=%.6g", epoch + 1, epochs,
-                    float(np.mean(epoch_loss)),
+                epoch_loss = torch.zeros(
+                    Gc, dtype=torch.float32, device=self.device
                 )
-            if es is None:
-                continue
-            upd = es.update(epoch, es.monitored(history))
-            if upd.capture.any():
-                # best weights of the models that improved
-                if best_p32 is None:
-                    best_p32 = torch.empty_like(self.store.p32)
-                self.store.copy_models(best_p32, self.store.p32, upd.capture)
-            if upd.stop.any():
-                self._restore_best(best_p32, upd.stop & es.has_best)
+                epoch_correct = torch.zeros(
+                    Gc, dtype=torch.float32, device=self.device
+                )
+                samples_seen = 0
+                for b in range(n_batches):
+                    idx = perm[:, b * batch_size : (b + 1) * batch_size]
+                    if idx.shape[1] == 0:
+                        continue
+                    Xb, Tb = cur._gather_batch(Xc, Yc, idx)
+                    loss = cur._graph_train_step(Xb, Tb)
+                    if loss is None:
+                        loss = cur.train_batch(Xb, Tb)
+                    epoch_loss += loss * idx.shape[1]
+                    epoch_correct += cur.last_correct
+                    samples_seen += idx.shape[1]
+                # loss and accuracy leave the device together: one
+                # transfer
+                epoch_stats = torch.stack(
+                    [epoch_loss, epoch_correct]
+                ) / max(samples_seen, 1)
+                epoch_loss, epoch_acc = epoch_stats.cpu().tolist()
+                history["loss"].append(row(epoch_loss))
+                history["accuracy"].append(row(epoch_acc))
+                if n_val > 0:
+                    val_loss = torch.zeros(
+                        Gc, dtype=torch.float32, device=self.device
+                    )
+                    val_correct = torch.zeros(
+                        Gc, dtype=torch.float32, device=self.device
+                    )
+                    vseen = 0
+                    for vs_ in range(n_train, n_all, batch_size):
+                        vidx = (
+                            torch.arange(
+                                vs_, min(vs_ + batch_size, n_all),
+                                device=self.device,
+                            ).unsqueeze(0).expand(Gc, -1)
+                        )
+                        Xvb, Tvb = cur._gather_batch(Xc, Yc, vidx)
+                        vl, vc = cur.eval_batch_stats(Xvb, Tvb)
+                        val_loss += vl * vidx.shape[1]
+                        val_correct += vc
+                        vseen += vidx.shape[1]
+                    val_losses, val_acc = (
+                        torch.stack([val_loss, val_correct]) / max(vseen, 1)
+                    ).cpu().tolist()
+                    history["val_loss"].append(row(val_losses))
+                    history["val_accuracy"].append(row(val_acc))
                 if verbose:
                     logger.info(
-                        "early stopping at epoch %d/%d: models %s",
-                        epoch + 1, epochs, np.nonzero(upd.stop)[0].tolist(),
+                        "epoch %d/%d mean-loss=%.6g", epoch + 1, epochs,
+                        float(np.nanmean(epoch_loss)),
                     )
-                if es.ended.all():
-                    break
-                if G > 1:  # the mask changed: upload it
-                    self.store.set_active(~es.ended)
-        if es is not None:
-            # models that ran to the epoch cap end here
-            self._restore_best(best_p32, ~es.ended & es.has_best)
+                if es is None:
+                    continue
+                # a compacted-out model's NaN never improves, and ended
+                # models are outside the rule anyway
+                upd = es.update(epoch, es.monitored(history))
+                if upd.capture.any():
+                    # best weights of the models that improved
+                    if cur_best is None:
+                        cur_best = torch.empty_like(cur.store.p32)
+                        if cur is self:
+                            best_p32 = cur_best
+                    cur.store.copy_models(
+                        cur_best, cur.store.p32, upd.capture[live]
+                    )
+                if upd.stop.any():
+                    cur._restore_best(
+                        cur_best, (upd.stop & es.has_best)[live]
+                    )
+                    if verbose:
+                        logger.info(
+                            "early stopping at epoch %d/%d: models %s",
+                            epoch + 1, epochs,
+                            np.nonzero(upd.stop)[0].tolist(),
+                        )
+                    if es.ended.all():
+                        break
+                    n_live = int((~es.ended).sum())
+                    if (
+                        compact_ratio is not None
+                        and epoch + 1 < epochs
+                        and should_compact(Gc, n_live, compact_ratio)
+                    ):
+                        # one hop is one simple mapping: the current
+                        # child goes back into this pack first, the
+                        # next one is gathered from this pack
+                        if cur is not self:
+                            best_p32 = self._absorb_child(
+                                cur, live, best_p32, cur_best
+                            )
+                            cur = self
+                            cur_best = None  # the child's buffers go
+                        live = np.nonzero(~es.ended)[0]
+                        cur, cur_best = self._live_child(live, best_p32)
+                        sel = torch.as_tensor(live, device=X.device)
+                        Xc = X.index_select(0, sel)
+                        Yc = Y.index_select(0, sel)
+                        history.compactions.append((epoch, Gc, cur.G))
+                        if verbose:
+                            logger.info(
+                                "pack compacted after epoch %d/%d: %d -> "
+                                "%d models", epoch + 1, epochs, Gc, cur.G,
+                            )
+                    elif Gc > 1:  # the mask changed: upload it
+                        cur.store.set_active((~es.ended)[live])
+            if es is not None:
+                # models that ran to the epoch cap end here
+                cur._restore_best(cur_best, (~es.ended & es.has_best)[live])
+            if cur is not self:
+                self._absorb_child(cur, live, None, None)
+                cur = self
+        finally:
+            if cur is not self:  # an error inside a child's epoch
+                cur.release_graphs()
         return epochs_done
+
+    def _live_child(self, live, best_p32):
+        """A pack of this pack's models ``live`` alone, in the state
+        they are in: parameters, mirror, optimizer slots, step counter
+        and (when held) best weights. Returns (child, its best-weights
+        buffer or None). Built from the gathered parameters, so no
+        weights are drawn; it decides ``_use_fused`` with its own G."""
+        child = type(self)(
+            self.spec, len(live), device=self.device,
+            seeds=[self.seeds[g] for g in live],
+            init_p32=self.store.gathered_p32(live),
+        )
+        assert (
+            child.store._total * self.G == self.store._total * child.G
+        ), "a child pack must lay its models out as its parent does"
+        child_best = None
+        if best_p32 is not None:
+            child_best = torch.empty_like(child.store.p32)
+        self.store.gather_models(
+            child.store, live,
+            None if best_p32 is None else (child_best, best_p32),
+        )
+        # masked from its first batch, as fit starts this pack: the
+        # train step is then never captured (nor re-captured) for G > 1
+        if child.G > 1:
+            child.store.set_active(np.ones(child.G, dtype=bool))
+        return child, child_best
+
+    def _absorb_child(self, child, live, best_p32, child_best):
+        """Scatter ``child`` back into this pack's models ``live`` and
+        drop it. With ``child_best`` its best weights go back too;
+        returns this pack's best-weights buffer."""
+        extra = None
+        if child_best is not None:
+            if best_p32 is None:
+                best_p32 = torch.empty_like(self.store.p32)
+            extra = (best_p32, child_best)
+        self.store.scatter_models(child.store, live, extra)
+        # captured graphs (a G = 1 child may hold one) go now, not at
+        # some later garbage collection
+        child.release_graphs()
+        return best_p32
 
     def _restore_best(self, best_p32, mask) -> None:
         """The masked models' weights (and mirror) become their best

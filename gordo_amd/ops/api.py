@@ -206,6 +206,29 @@ def masked_copy(dst, src, mask, table, dst_lp=None):
     return ref.masked_copy(dst, src, mask, table, dst_lp)
 
 
+def remap_models(dst, src, dst_index, src_index, dst_table, src_table,
+                 G_dst, G_src, dst_lp=None):
+    """Move whole models between two flat fp32 buffers of different G
+    (pack compaction): for every pair j, the slices of model
+    ``src_index[j]`` of ``src`` ([G_src, per_s] tensors at
+    ``src_table``'s offsets) are written to model ``dst_index[j]`` of
+    ``dst`` ([G_dst, per_s] at ``dst_table``'s) and, rounded as
+    ``masked_copy`` rounds, into the bf16 mirror ``dst_lp``; every
+    other element of ``dst`` / ``dst_lp`` keeps its bits. The index
+    sequences are host ints and are checked before anything is
+    launched (ValueError): equal length >= 1, every entry inside its
+    side's G, no model twice in ``dst_index``."""
+    di, si = ref.check_model_pairs(dst_index, src_index, G_dst, G_src)
+    if _on_gpu(dst):
+        return _require_hip().remap_models(
+            dst, src, di, si, dst_table, src_table, int(G_dst), int(G_src),
+            dst_lp,
+        )
+    return ref.remap_models(
+        dst, src, di, si, dst_table, src_table, G_dst, G_src, dst_lp
+    )
+
+
 def optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp=None,
                    step_buf=None, active=None, segments=None):
     """One fused optimizer step over the flat fp32 master buffer (+

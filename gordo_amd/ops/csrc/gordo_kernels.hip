@@ -1030,6 +1030,11 @@ void optimizer_step_masked(int64_t kind, torch::Tensor p, torch::Tensor g,
                            torch::Tensor table);
 void masked_copy(torch::Tensor dst, torch::Tensor src, torch::Tensor mask,
                  torch::Tensor table, c10::optional<torch::Tensor> dst_lp);
+void remap_models(torch::Tensor dst, torch::Tensor src,
+                  std::vector<int64_t> dst_index,
+                  std::vector<int64_t> src_index, torch::Tensor dst_table,
+                  torch::Tensor src_table, int64_t G_dst, int64_t G_src,
+                  c10::optional<torch::Tensor> dst_lp);
 }  // namespace gordo_masked
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -1041,6 +1046,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("dst_lp") = py::none(),
           "copy the slices of the models with mask[g] != 0 (+ bf16 "
           "mirror)");
+  mod.def("remap_models", &gordo_masked::remap_models, py::arg("dst"),
+          py::arg("src"), py::arg("dst_index"), py::arg("src_index"),
+          py::arg("dst_table"), py::arg("src_table"), py::arg("G_dst"),
+          py::arg("G_src"), py::arg("dst_lp") = py::none(),
+          "write models src_index of a [G_src, ...] flat buffer to models "
+          "dst_index of a [G_dst, ...] one (+ bf16 mirror)");
   mod.def("loss_bwd", &gordo_train::loss_bwd,
           "fused per-model loss (mse/mae/huber/logcosh) + grad + "
           "accuracy count, one pass over (Y, T)");

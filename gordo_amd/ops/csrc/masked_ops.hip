@@ -5,6 +5,10 @@
 //                          active[g] == 0
 //   masked_copy            dst <- src (+ bf16 mirror) for the models
 //                          whose mask[g] != 0
+//   remap_models           whole models from a [G_src, ...] buffer into
+//                          a [G_dst, ...] buffer (+ bf16 mirror), by a
+//                          list of (dst model, src model) pairs: pack
+//                          compaction (see remap_models_kernel)
 //
 // The flat buffer holds S declared tensors; tensor s is [G, per_s], so
 // model g owns [off_s + g*per_s, off_s + (g+1)*per_s). The segment
@@ -305,6 +309,100 @@ __global__ void masked_copy_kernel(float* __restrict__ dst,
       });
 }
 
+// walk_model_units between two layouts: the same S tensors, [G_dst,
+// per_s] at off_dst[s] in one buffer and [G_src, per_s] at off_src[s]
+// in the other. Lane t < S checks segment t against BOTH tables
+// (segment_slice on each side; a per that differs between them skips
+// the segment too) and the unit table holds the two bases of the pair's
+// models gd and gs. vec4(ed, es) / one(ed, es) get the flat element
+// index on either side. A segment moves as 16-byte vectors only when
+// both of its bases are multiples of 4: off_dst = sum G_dst*per_k can
+// be aligned where off_src = sum G_src*per_k is not, and the reverse.
+template <class FV, class FS>
+MK_DEV_INLINE void walk_pair_units(const long long* __restrict__ dtab,
+                                   const long long* __restrict__ stab, int S,
+                                   int gd, int G_dst, size_t n_dst,
+                                   size_t nm_dst, int gs, int G_src,
+                                   size_t n_src, size_t nm_src, int vec_ok,
+                                   FV&& vec4, FS&& one) {
+  __shared__ size_t sh_dbase[MAX_SEGMENTS], sh_sbase[MAX_SEGMENTS];
+  __shared__ size_t sh_per[MAX_SEGMENTS];
+  __shared__ size_t sh_units[MAX_SEGMENTS], sh_first[MAX_SEGMENTS];
+  __shared__ size_t sh_total;
+  __shared__ int sh_seg;
+  const int t = threadIdx.x;
+  size_t my_units = 0;
+  if (t < S) {
+    size_t dbase = 0, sbase = 0, dper = 0, sper = 0;
+    const bool okd =
+        segment_slice(dtab, S, t, gd, G_dst, n_dst, nm_dst, dbase, dper);
+    const bool oks =
+        segment_slice(stab, S, t, gs, G_src, n_src, nm_src, sbase, sper);
+    if (okd && oks && dper == sper)
+      my_units = (dper + UNIT - 1) >> UNIT_SHIFT;
+    sh_dbase[t] = dbase;
+    sh_sbase[t] = sbase;
+    sh_per[t] = dper;
+    sh_units[t] = my_units;
+  }
+  __syncthreads();
+  size_t my_first = 0;
+  if (t < S) {
+    for (int j = 0; j < t; ++j) my_first += sh_units[j];
+    sh_first[t] = my_first;
+    if (t == S - 1) sh_total = my_first + my_units;
+  }
+  __syncthreads();
+  const size_t total = sh_total;
+  // the trip count depends on blockIdx and total alone: uniform
+  for (size_t u = blockIdx.x; u < total; u += gridDim.x) {
+    if (t < S && u >= my_first && u < my_first + my_units) sh_seg = t;
+    __syncthreads();
+    const int s = sh_seg;
+    const size_t dbase = sh_dbase[s], sbase = sh_sbase[s], per = sh_per[s];
+    const size_t first = sh_first[s];
+    __syncthreads();  // sh_seg is read: the next round may write it
+    const size_t lo = (u - first) << UNIT_SHIFT;
+    const size_t hi = lo + UNIT < per ? lo + UNIT : per;
+    if (vec_ok && (per & 3) == 0 && (dbase & 3) == 0 && (sbase & 3) == 0) {
+      const size_t i = lo + ((size_t)threadIdx.x << 2);
+      if (i < hi) vec4(dbase + i, sbase + i);  // hi % 4 == 0
+    } else {
+      for (size_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
+        one(dbase + i, sbase + i);
+    }
+  }
+}
+
+// Pack compaction: pair j = blockIdx.y writes the slices of model
+// pairs[P + j] of src, in all S tensors, to model pairs[j] of dst (and
+// rounded into dst's bf16 mirror). Grid (chunks, P), 256 threads. The
+// host entry has validated the pairs; a pair outside either G is
+// dropped here as a whole block all the same, before any barrier.
+__global__ void remap_models_kernel(
+    float* __restrict__ dst, const float* __restrict__ src,
+    bf16* __restrict__ dlp, size_t n_dst, size_t n_src,
+    const int* __restrict__ pairs, int P, const long long* __restrict__ dtab,
+    const long long* __restrict__ stab, int S, int G_dst, int G_src,
+    int vec_ok, size_t nm_dst, size_t nm_src) {
+  const int gd = pairs[blockIdx.y];
+  const int gs = pairs[P + blockIdx.y];
+  if (gd < 0 || gd >= G_dst || gs < 0 || gs >= G_src) return;
+  walk_pair_units(
+      dtab, stab, S, gd, G_dst, n_dst, nm_dst, gs, G_src, n_src, nm_src,
+      vec_ok,
+      [&](size_t ed, size_t es) {
+        float4 v = *reinterpret_cast<const float4*>(src + es);
+        *reinterpret_cast<float4*>(dst + ed) = v;
+        if (dlp) store_bf16x4(dlp + ed, v);
+      },
+      [&](size_t ed, size_t es) {
+        float v = src[es];
+        dst[ed] = v;
+        if (dlp) dlp[ed] = f2bf(v);
+      });
+}
+
 // the step counter bump of the unmasked entries, launched the same way
 __global__ void masked_bump_kernel(int* step_buf) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *step_buf += 1;
@@ -474,6 +572,88 @@ void masked_copy(torch::Tensor dst, torch::Tensor src, torch::Tensor mask,
                      src.data_ptr<float>(), lp_ptr, n, mask.data_ptr<int>(),
                      (const long long*)table.data_ptr<int64_t>(), S,
                      vec ? 1 : 0, n / (size_t)G);
+}
+
+void remap_models(torch::Tensor dst, torch::Tensor src,
+                  std::vector<int64_t> dst_index,
+                  std::vector<int64_t> src_index, torch::Tensor dst_table,
+                  torch::Tensor src_table, int64_t G_dst, int64_t G_src,
+                  c10::optional<torch::Tensor> dst_lp) {
+  TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == torch::kFloat32 &&
+                  dst.is_contiguous(),
+              "dst must be a contiguous fp32 GPU tensor");
+  TORCH_CHECK(src.is_cuda() && src.scalar_type() == torch::kFloat32 &&
+                  src.is_contiguous() &&
+                  src.get_device() == dst.get_device(),
+              "src must be a contiguous fp32 tensor on dst's device");
+  TORCH_CHECK(G_dst >= 1 && G_dst <= 65535 && G_src >= 1 && G_src <= 65535,
+              "G_dst and G_src must be in [1, 65535]");
+  for (const torch::Tensor* t : {&dst_table, &src_table}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kInt64 &&
+                    t->is_contiguous() && t->dim() == 2 && t->size(0) == 2 &&
+                    t->get_device() == dst.get_device(),
+                "a segment table must be a contiguous int64 [2, S] tensor "
+                "on the buffers' device");
+  }
+  int64_t S = dst_table.size(1);
+  TORCH_CHECK(src_table.size(1) == S,
+              "the two segment tables must hold the same tensors");
+  TORCH_CHECK(S >= 1 && S <= MAX_SEGMENTS, "the segment table holds ", S,
+              " tensors; the masked kernels take 1 to ", MAX_SEGMENTS);
+  // the pairs, checked on the host: nothing below may launch on a
+  // list that leaves either buffer
+  size_t P = dst_index.size();
+  TORCH_CHECK(P >= 1 && src_index.size() == P,
+              "dst_index and src_index must have the same length >= 1");
+  std::vector<char> seen((size_t)G_dst, 0);
+  for (size_t j = 0; j < P; ++j) {
+    TORCH_CHECK(dst_index[j] >= 0 && dst_index[j] < G_dst,
+                "dst_index[", j, "] = ", dst_index[j], " is outside [0, ",
+                G_dst, ")");
+    TORCH_CHECK(src_index[j] >= 0 && src_index[j] < G_src,
+                "src_index[", j, "] = ", src_index[j], " is outside [0, ",
+                G_src, ")");
+    TORCH_CHECK(!seen[(size_t)dst_index[j]], "dst_index holds model ",
+                dst_index[j], " twice");
+    seen[(size_t)dst_index[j]] = 1;
+  }
+  size_t n_dst = dst.numel(), n_src = src.numel();
+  TORCH_CHECK(n_dst % (size_t)G_dst == 0 && n_src % (size_t)G_src == 0,
+              "each buffer's size must be a multiple of its G");
+  bool vec = aligned16(dst.data_ptr()) && aligned16(src.data_ptr());
+  bf16* lp_ptr = nullptr;
+  if (dst_lp.has_value()) {
+    TORCH_CHECK(dst_lp->is_cuda() &&
+                    dst_lp->scalar_type() == torch::kBFloat16 &&
+                    dst_lp->is_contiguous() &&
+                    (size_t)dst_lp->numel() == n_dst &&
+                    dst_lp->get_device() == dst.get_device(),
+                "dst_lp must be a bf16 mirror of dst");
+    lp_ptr = (bf16*)dst_lp->data_ptr();
+    vec = vec && aligned16(lp_ptr);
+  }
+  if (n_dst == 0 || n_src == 0) return;
+  // both index lists travel as one int32 [2, P] tensor
+  auto pairs_h = torch::empty({2, (int64_t)P}, torch::kInt32);
+  int* ph = pairs_h.data_ptr<int>();
+  for (size_t j = 0; j < P; ++j) {
+    ph[j] = (int)dst_index[j];
+    ph[P + j] = (int)src_index[j];
+  }
+  auto pairs = pairs_h.to(dst.device());
+  // one block per unit of a model, as chunks_for, with the grid capped
+  // by the number of pairs
+  size_t want = ((n_dst / (size_t)G_dst) >> UNIT_SHIFT) + (size_t)S;
+  size_t cap = std::max<size_t>(1, 4096 / P);
+  int chunks = (int)std::max<size_t>(1, std::min(want, cap));
+  hipLaunchKernelGGL(remap_models_kernel, dim3(chunks, (unsigned)P),
+                     dim3(256), 0, cur_stream(), dst.data_ptr<float>(),
+                     src.data_ptr<float>(), lp_ptr, n_dst, n_src,
+                     pairs.data_ptr<int>(), (int)P,
+                     (const long long*)dst_table.data_ptr<int64_t>(),
+                     (const long long*)src_table.data_ptr<int64_t>(), (int)S,
+                     (int)G_dst, (int)G_src, vec ? 1 : 0,
+                     n_dst / (size_t)G_dst, n_src / (size_t)G_src);
 }
 
 }  // namespace gordo_masked

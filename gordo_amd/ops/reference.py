@@ -320,6 +320,64 @@ def masked_copy(
             d[rows] = s[rows].to(dst_lp.dtype)
 
 
+def check_model_pairs(dst_index, src_index, G_dst: int, G_src: int):
+    """The (dst model, src model) pairs of ``remap_models`` as two int
+    lists. Raises ValueError unless they have the same length >= 1,
+    every entry lies in [0, G) of its side and ``dst_index`` holds no
+    model twice."""
+    di = [int(i) for i in dst_index]
+    si = [int(i) for i in src_index]
+    if len(di) != len(si) or not di:
+        raise ValueError(
+            "dst_index and src_index must have the same length >= 1, got "
+            f"{len(di)} and {len(si)}"
+        )
+    for name, idx, G in (("dst", di, G_dst), ("src", si, G_src)):
+        bad = [i for i in idx if not 0 <= i < int(G)]
+        if bad:
+            raise ValueError(
+                f"{name}_index entries {bad} are outside [0, {int(G)})"
+            )
+    if len(set(di)) != len(di):
+        raise ValueError(f"dst_index holds a model twice: {di}")
+    return di, si
+
+
+def remap_models(
+    dst: torch.Tensor,
+    src: torch.Tensor,
+    dst_index,
+    src_index,
+    dst_table: torch.Tensor,
+    src_table: torch.Tensor,
+    G_dst: int,
+    G_src: int,
+    dst_lp: Optional[torch.Tensor] = None,
+):
+    """Whole models between two flat buffers of different G: tensor s
+    is [G_src, per_s] at ``src_table[0, s]`` in ``src`` and [G_dst,
+    per_s] at ``dst_table[0, s]`` in ``dst``. For every pair j the
+    slices of model ``src_index[j]`` of ``src`` are written to model
+    ``dst_index[j]`` of ``dst`` (and, in its own precision, of
+    ``dst_lp``). Everything else stays as it is; a segment whose size
+    differs between the tables is skipped."""
+    di, si = check_model_pairs(dst_index, src_index, G_dst, G_src)
+    G_dst, G_src = int(G_dst), int(G_src)
+    di_t = torch.tensor(di, dtype=torch.long, device=dst.device)
+    si_t = torch.tensor(si, dtype=torch.long, device=src.device)
+    for (doff, dper), (soff, sper) in zip(
+        zip(*dst_table.tolist()), zip(*src_table.tolist())
+    ):
+        if dper != sper or dper <= 0:
+            continue
+        rows = src[soff : soff + G_src * sper].view(G_src, sper)[si_t]
+        dst[doff : doff + G_dst * dper].view(G_dst, dper)[di_t] = rows
+        if dst_lp is not None:
+            dst_lp[doff : doff + G_dst * dper].view(G_dst, dper)[di_t] = (
+                rows.to(dst_lp.dtype)
+            )
+
+
 def optimizer_step_masked(
     kind: str,
     p: torch.Tensor,
