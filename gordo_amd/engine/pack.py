@@ -139,13 +139,24 @@ class _ParamStore:
         # with early stopping and G > 1 sets it.
         self.active: Optional[torch.Tensor] = None
         self._segments: Optional[torch.Tensor] = None
+        # weight regularizers: (l1, l2) per declared tensor, and the
+        # float32 [2, S] device table built from them on first use
+        self._regs: Dict[str, Tuple[float, float]] = {}
+        self._reg_table: Optional[torch.Tensor] = None
+        # [G] penalty at the weights the latest optimizer_step started
+        # from (the weights that batch's forward pass used)
+        self.last_penalty: Optional[torch.Tensor] = None
 
     def declare(self, name: str, shape: Tuple[int, ...],
-                logical: Optional[Tuple[int, ...]] = None):
+                logical: Optional[Tuple[int, ...]] = None,
+                reg: Tuple[float, float] = (0.0, 0.0)):
+        """``reg``: the (l1, l2) weight-regularizer coefficients of this
+        tensor (l1 sum|w| + l2 sum w^2 joins the model's loss)."""
         n = int(np.prod(shape))
         self._offsets[name] = (self._total, n)
         self._shapes.append((name, shape))
         self.logical[name] = tuple(logical) if logical else tuple(shape)
+        self._regs[name] = (float(reg[0]), float(reg[1]))
         self._total += n
 
     def allocate(self):
@@ -196,6 +207,34 @@ class _ParamStore:
                 self.device,
             )
         return self._segments
+
+    @property
+    def regularized(self) -> bool:
+        return any(l1 or l2 for l1, l2 in self._regs.values())
+
+    @property
+    def reg_table(self) -> Optional[torch.Tensor]:
+        """float32 [2, S] coefficient table beside ``segments`` (l1
+        row, l2 row), built once; None when every coefficient is zero:
+        such a store steps and reports exactly as one without
+        regularizers."""
+        if self._reg_table is None and self.regularized:
+            self._reg_table = ops.reg_table(
+                [self._regs[name][0] for name, _ in self._shapes],
+                [self._regs[name][1] for name, _ in self._shapes],
+                self.device,
+            )
+        return self._reg_table
+
+    def weight_penalty(self) -> Optional[torch.Tensor]:
+        """[G] penalty of the current weights; None without
+        regularizers."""
+        reg = self.reg_table
+        if reg is None:
+            return None
+        return ops.weight_penalty(
+            self.p32, self.segments, reg, self.n_models
+        )
 
     def set_active(self, active) -> None:
         """Upload the [G] mask of the models that still train (None:
@@ -302,6 +341,19 @@ class _ParamStore:
         """One step of the spec's optimizer over the whole buffer, or,
         while ``active`` is set, over the models that still train."""
         self.step_count += 1
+        reg = self.reg_table
+        if reg is not None:
+            # the penalty belongs to the loss of this batch, at the
+            # weights its forward pass used: before they move. The step
+            # is the segment-aware one, with or without a mask.
+            self.last_penalty = self.weight_penalty()
+            ops.optimizer_step(
+                self.optimizer_kind, self.p32, self.g32, self.m, self.v,
+                self.vhat, self.optimizer_params, self.step_count, self.plp,
+                step_buf=self.step_buf, active=self.active,
+                segments=self.segments, reg=reg, G=self.n_models,
+            )
+            return
         # active None (no early stopping, or G = 1): the unmasked kernels
         ops.optimizer_step(
             self.optimizer_kind, self.p32, self.g32, self.m, self.v,
@@ -521,6 +573,9 @@ class BasePack:
             and self.device.type == "cuda"
             # a masked step (per-model early stopping) runs eagerly
             and self.store.active is None
+            # so does a regularized one: its step is the segment-aware
+            # kernel too, and the penalty launch is not captured
+            and not self.store.regularized
         ):
             # _graph_enabled False (set per-instance after a capture
             # failure) wins; otherwise the env is re-read so flipping
@@ -798,6 +853,9 @@ class BasePack:
                     loss = cur._graph_train_step(Xb, Tb)
                     if loss is None:
                         loss = cur.train_batch(Xb, Tb)
+                    if cur.store.regularized:
+                        # Keras reports data loss + weight penalty
+                        loss = loss + cur.store.last_penalty
                     epoch_loss += loss * idx.shape[1]
                     epoch_correct += cur.last_correct
                     samples_seen += idx.shape[1]
@@ -829,9 +887,14 @@ class BasePack:
                         val_loss += vl * vidx.shape[1]
                         val_correct += vc
                         vseen += vidx.shape[1]
-                    val_losses, val_acc = (
+                    val_stats = (
                         torch.stack([val_loss, val_correct]) / max(vseen, 1)
-                    ).cpu().tolist()
+                    )
+                    # once per validation pass: the weights do not move
+                    val_penalty = cur.store.weight_penalty()
+                    if val_penalty is not None:
+                        val_stats[0] += val_penalty
+                    val_losses, val_acc = val_stats.cpu().tolist()
                     history["val_loss"].append(row(val_losses))
                     history["val_accuracy"].append(row(val_acc))
                 if verbose:
@@ -983,10 +1046,12 @@ class DensePack(BasePack):
         self._logical_out = dims[-1][1]
         for i, (fin, fout, _act, _l1) in enumerate(self.layer_meta):
             lfin, lfout = dims[i][0], dims[i][1]
+            regs = self.spec.layers[i].weight_regs()
             self.store.declare(f"W{i}", (self.G, fin, fout),
-                               logical=(self.G, lfin, lfout))
+                               logical=(self.G, lfin, lfout),
+                               reg=regs["kernel"])
             self.store.declare(f"b{i}", (self.G, fout),
-                               logical=(self.G, lfout))
+                               logical=(self.G, lfout), reg=regs["bias"])
 
     def _init_weights(self):
         for g in range(self.G):
@@ -1102,12 +1167,16 @@ class LSTMPack(BasePack):
         for i, layer in enumerate(lstm_layers):
             H_l = layer.units
             fin, H = p(fin_l), p(H_l)
+            # each regularizer covers all four gates of its tensor
+            regs = layer.weight_regs()
             self.store.declare(f"Wx{i}", (self.G, fin, 4 * H),
-                               logical=(self.G, fin_l, 4 * H_l))
+                               logical=(self.G, fin_l, 4 * H_l),
+                               reg=regs["kernel"])
             self.store.declare(f"Wh{i}", (self.G, H, 4 * H),
-                               logical=(self.G, H_l, 4 * H_l))
+                               logical=(self.G, H_l, 4 * H_l),
+                               reg=regs["recurrent"])
             self.store.declare(f"bl{i}", (self.G, 4 * H),
-                               logical=(self.G, 4 * H_l))
+                               logical=(self.G, 4 * H_l), reg=regs["bias"])
             if H != H_l or fin != fin_l:
                 self._extractors[f"Wx{i}"] = self._gate_converters(
                     H_l, H, fin_l
@@ -1125,10 +1194,13 @@ class LSTMPack(BasePack):
         self._logical_out = out_layer.units
         self.dense_meta = (p(fin_l), p(out_layer.units), out_layer.activation)
         self.dense_meta_logical = (fin_l, out_layer.units, out_layer.activation)
+        out_regs = out_layer.weight_regs()
         self.store.declare("Wd", (self.G, p(fin_l), p(out_layer.units)),
-                           logical=(self.G, fin_l, out_layer.units))
+                           logical=(self.G, fin_l, out_layer.units),
+                           reg=out_regs["kernel"])
         self.store.declare("bd", (self.G, p(out_layer.units)),
-                           logical=(self.G, out_layer.units))
+                           logical=(self.G, out_layer.units),
+                           reg=out_regs["bias"])
 
     def _init_weights(self):
         # draw the LOGICAL matrices in the same RNG order as the

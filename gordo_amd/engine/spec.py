@@ -207,6 +207,95 @@ def _freeze(v: Any) -> Any:
     return v
 
 
+# ---- weight regularizers ----------------------------------------------
+# LayerSpec field pairs, in the order arch_key and to_dict list them
+_REG_FIELDS = ("kernel_l1", "kernel_l2", "bias_l1", "bias_l2",
+               "recurrent_l1", "recurrent_l2")
+# Keras regularizer names (last path component, lower-cased) -> the
+# (l1, l2) defaults of that class; None: the class has no such term
+_REGULARIZER_DEFAULTS = {
+    "l1l2": (0.0, 0.0),
+    "l1": (0.01, None),
+    "l2": (None, 0.01),
+    "l1_l2": (0.01, 0.01),
+}
+
+
+def _reg_coefficient(owner: str, key: str, v: Any) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError(
+            f"Unsupported {owner} coefficient {key}={v!r}: not a number"
+        )
+    v = float(v)
+    if not (v >= 0.0 and v != float("inf")):
+        raise ValueError(
+            f"Unsupported {owner} coefficient {key}={v!r}: must be a "
+            "finite number >= 0"
+        )
+    return v
+
+
+def parse_weight_regularizer(reg_def: Any, owner: str = "regularizer"
+                             ) -> Tuple[float, float]:
+    """(l1, l2) of a Keras weight regularizer definition: ``None``; one
+    of the strings ``"l1"``, ``"l2"``, ``"l1_l2"`` (0.01 each); a
+    single-key dict ``{"...L1L2": {"l1": a, "l2": b}}`` (defaults 0, 0),
+    ``{"...L1": {"l1": a}}``, ``{"...L2": {"l2": b}}`` (default 0.01) or
+    ``{"...l1_l2": {...}}`` (defaults 0.01, 0.01), the class name
+    case-insensitive; or a plain ``{"l1": a, "l2": b}``. Anything else
+    raises ValueError naming the offender (``owner`` says which
+    setting it came from).
+
+    >>> parse_weight_regularizer({"keras.regularizers.L1L2": {"l1": 0.2}})
+    (0.2, 0.0)
+    >>> parse_weight_regularizer("l2")
+    (0.0, 0.01)
+    """
+    if reg_def is None:
+        return 0.0, 0.0
+    if isinstance(reg_def, str):
+        name = reg_def.rsplit(".", 1)[-1].lower()
+        if name not in ("l1", "l2", "l1_l2"):
+            raise ValueError(f"Unsupported {owner} {reg_def!r}")
+        l1, l2 = _REGULARIZER_DEFAULTS[name]
+        return l1 or 0.0, l2 or 0.0
+    if not isinstance(reg_def, dict) or not reg_def:
+        raise ValueError(f"Unsupported {owner} {reg_def!r}")
+    if all(k in ("l1", "l2") for k in reg_def):
+        # the plain form; a lone key whose value is a dict is the
+        # class form with a lower-case name: {"l1": {"l1": a}}
+        lone = next(iter(reg_def.values())) if len(reg_def) == 1 else 0
+        if not isinstance(lone, dict):
+            return (
+                _reg_coefficient(owner, "l1", reg_def.get("l1", 0.0)),
+                _reg_coefficient(owner, "l2", reg_def.get("l2", 0.0)),
+            )
+    if len(reg_def) != 1:
+        bad = sorted(str(k) for k in reg_def if k not in ("l1", "l2"))
+        raise ValueError(
+            f"Unsupported {owner} {reg_def!r}: unknown key {bad[0]!r}"
+        )
+    cls_name, kwargs = next(iter(reg_def.items()))
+    name = str(cls_name).rsplit(".", 1)[-1].lower()
+    if name not in _REGULARIZER_DEFAULTS:
+        raise ValueError(
+            f"Unsupported {owner} class {cls_name!r}; supported: L1, L2, "
+            "L1L2, l1_l2"
+        )
+    if kwargs is not None and not isinstance(kwargs, dict):
+        raise ValueError(
+            f"Unsupported {owner} arguments {kwargs!r} for {cls_name!r}"
+        )
+    out = dict(zip(("l1", "l2"), _REGULARIZER_DEFAULTS[name]))
+    for k, v in (kwargs or {}).items():
+        if k not in out or out[k] is None:
+            raise ValueError(
+                f"Unsupported {owner} key {k!r} for {cls_name!r}"
+            )
+        out[k] = _reg_coefficient(owner, k, v)
+    return out["l1"] or 0.0, out["l2"] or 0.0
+
+
 @dataclass
 class LayerSpec:
     kind: str  # "dense" | "lstm"
@@ -214,13 +303,56 @@ class LayerSpec:
     activation: str = "tanh"
     l1_activity: float = 0.0  # L1 activity regularizer weight (dense)
     return_sequences: bool = True  # lstm only
+    # weight regularizers (Keras kernel_ / bias_ / recurrent_regularizer):
+    # each adds l1 sum|w| + l2 sum w^2 over its tensor to the model's
+    # loss. The recurrent pair is legal only on lstm.
+    kernel_l1: float = 0.0
+    kernel_l2: float = 0.0
+    bias_l1: float = 0.0
+    bias_l2: float = 0.0
+    recurrent_l1: float = 0.0
+    recurrent_l2: float = 0.0
+
+    def __post_init__(self):
+        for name in _REG_FIELDS:
+            setattr(self, name, _reg_coefficient(
+                f"{self.kind} layer", name, getattr(self, name)
+            ))
+        if self.kind != "lstm" and (self.recurrent_l1 or self.recurrent_l2):
+            raise ValueError(
+                f"recurrent_regularizer on a {self.kind} layer: only LSTM "
+                "layers have a recurrent kernel"
+            )
+
+    def __setstate__(self, state):
+        # a layer pickled before the weight regularizers existed
+        self.__dict__.update(state)
+        for name in _REG_FIELDS:
+            self.__dict__.setdefault(name, 0.0)
+
+    def weight_regs(self) -> Dict[str, Tuple[float, float]]:
+        """(l1, l2) per tensor role: kernel, recurrent, bias."""
+        return {
+            "kernel": (self.kernel_l1, self.kernel_l2),
+            "recurrent": (self.recurrent_l1, self.recurrent_l2),
+            "bias": (self.bias_l1, self.bias_l2),
+        }
 
     def to_dict(self) -> Dict[str, Any]:
-        return asdict(self)
+        return _layer_dict(asdict(self))
 
     @classmethod
     def from_dict(cls, d) -> "LayerSpec":
         return cls(**d)
+
+
+def _layer_dict(d: Dict[str, Any]) -> Dict[str, Any]:
+    """A layer's dict without the regularizer fields when all are zero:
+    an unregularized layer's dict is what it was before they existed."""
+    if not any(d[name] for name in _REG_FIELDS):
+        for name in _REG_FIELDS:
+            del d[name]
+    return d
 
 
 @dataclass
@@ -267,6 +399,7 @@ class ModelSpec:
 
     def to_dict(self) -> Dict[str, Any]:
         d = asdict(self)
+        d["layers"] = [_layer_dict(x) for x in d["layers"]]
         if not d["loss_kwargs"]:
             del d["loss_kwargs"]
         if d["lstm_act_version"] == 1:
@@ -289,6 +422,11 @@ class ModelSpec:
             dims.append((prev, layer.units, layer.activation, layer.l1_activity))
             prev = layer.units
         return dims
+
+    def has_weight_regularizers(self) -> bool:
+        return any(
+            getattr(l, name) for l in self.layers for name in _REG_FIELDS
+        )
 
     def lstm_activations(self) -> List[str]:
         """Canonical cell activation each LSTM layer RUNS, in layer
@@ -319,7 +457,11 @@ class ModelSpec:
             self.n_features,
             self.n_features_out,
             tuple(
-                (l.kind, l.units, l.activation, l.l1_activity, l.return_sequences)
+                (l.kind, l.units, l.activation, l.l1_activity,
+                 l.return_sequences)
+                # per tensor, not per model: differently regularized
+                # models do not share a pack
+                + tuple(getattr(l, name) for name in _REG_FIELDS)
                 for l in self.layers
             ),
             self.lookback_window,

@@ -26,7 +26,12 @@ from .base import GordoBase
 from .register import register_model_builder
 from ...core.import_utils import import_location
 from ...engine.pack import DensePack, LSTMPack
-from ...engine.spec import LayerSpec, ModelSpec, parse_compile_kwargs
+from ...engine.spec import (
+    LayerSpec,
+    ModelSpec,
+    parse_compile_kwargs,
+    parse_weight_regularizer,
+)
 
 logger = logging.getLogger(__name__)
 
@@ -499,6 +504,7 @@ def _parse_raw_spec(
                     units=int(lkw.get("units", n_features_out)),
                     activation=lkw.get("activation", "linear") or "linear",
                     l1_activity=_raw_l1(lkw.get("activity_regularizer")),
+                    **_raw_weight_regs(lname, lkw),
                 )
             )
         elif lname == "LSTM":
@@ -516,6 +522,7 @@ def _parse_raw_spec(
                     # Keras' LSTM default; None is linear, as in Keras
                     activation=lkw.get("activation", "tanh"),
                     return_sequences=bool(lkw.get("return_sequences", False)),
+                    **_raw_weight_regs(lname, lkw),
                 )
             )
         else:
@@ -557,6 +564,27 @@ def _parse_raw_spec(
         optimizer=optimizer,
         optimizer_kwargs=opt_kw,
     )
+
+
+def _raw_weight_regs(lname: str, lkw: dict) -> dict:
+    """The LayerSpec coefficient fields of a raw layer's
+    ``kernel_regularizer`` / ``bias_regularizer`` /
+    ``recurrent_regularizer`` (Keras: each adds l1 sum|w| + l2 sum w^2
+    over its tensor to the loss). ``recurrent_regularizer`` is an LSTM
+    setting; on another layer it raises, as Keras does."""
+    out = {}
+    for role in ("kernel", "bias", "recurrent"):
+        key = f"{role}_regularizer"
+        if key not in lkw:
+            continue
+        if role == "recurrent" and lname != "LSTM":
+            raise ValueError(
+                f"Unsupported {key} on a {lname} layer: only LSTM layers "
+                "have a recurrent kernel"
+            )
+        l1, l2 = parse_weight_regularizer(lkw[key], f"{lname} {key}")
+        out[f"{role}_l1"], out[f"{role}_l2"] = l1, l2
+    return out
 
 
 def _raw_l1(reg_def) -> float:

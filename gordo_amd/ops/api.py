@@ -229,8 +229,38 @@ def remap_models(dst, src, dst_index, src_index, dst_table, src_table,
     )
 
 
+def reg_table(l1, l2, device=None):
+    """float32 [2, S] regularizer table beside a ``segment_table``: row
+    0 the l1 and row 1 the l2 coefficient of each of the S tensors."""
+    return ref.reg_table(l1, l2, device)
+
+
+def weight_penalty(p, table, reg, G):
+    """Per-model weight penalty of the flat fp32 buffer ``p``:
+    ``sum_s (l1_s sum|w_s| + l2_s sum w_s^2)`` over the tensors of
+    ``table`` with the coefficients of ``reg`` (``reg_table``), float32
+    [G]. Reads ``p`` only. On GPU a model's result bits depend on that
+    model's values alone: not on G, on its place in the pack, on the
+    alignment of its slices or on the launch (no atomics; see
+    docs/kernels.md, "Weight regularizers")."""
+    if _on_gpu(p):
+        return _require_hip().weight_penalty(p, table, reg, int(G))
+    return ref.weight_penalty(p, table, reg, int(G))
+
+
+def last_optimizer_launch() -> dict:
+    """Which optimizer kernel this thread's last GPU ``optimizer_step``
+    / ``adam_step`` launched: ``family`` ("adam": adam_kernel, "opt":
+    opt_kernel<KIND>, "masked": the segment-aware opt_masked_kernel)
+    and ``reg`` (the weight regularizers' gradient term was fused in).
+    Host-side record; ``family`` is "" before any launch."""
+    family, reg = _require_hip().last_optimizer_launch()
+    return {"family": family, "reg": bool(reg)}
+
+
 def optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp=None,
-                   step_buf=None, active=None, segments=None):
+                   step_buf=None, active=None, segments=None, reg=None,
+                   G=None):
     """One fused optimizer step over the flat fp32 master buffer (+
     bf16 mirror refresh). ``kind``/``hyper`` are the spec's canonical
     optimizer name and complete ``optimizer_params``. On GPU the step
@@ -239,26 +269,52 @@ def optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp=None,
     With ``active`` (int32 [G]) and ``segments`` (``segment_table``)
     the step takes the masked entry: a model with ``active[g] == 0`` is
     neither read nor written, an active one gets exactly the unmasked
-    arithmetic. Without ``active`` the unmasked kernels run."""
-    if active is not None and segments is None:
-        raise ValueError("a masked optimizer_step needs the segment table")
+    arithmetic. Without ``active`` the unmasked kernels run.
+
+    With ``reg`` (``reg_table``, beside ``segments``) the optimizer
+    sees ``g + (l1 sgn(p) + 2 l2 p)`` for every tensor with a non-zero
+    coefficient (``sgn(±0) = 0``); ``g`` is not modified. The step is
+    then the segment-aware one with or without ``active``; without it
+    ``G`` (the number of models) must be given."""
+    if (active is not None or reg is not None) and segments is None:
+        raise ValueError(
+            "a masked or regularized optimizer_step needs the segment table"
+        )
+    if reg is not None and active is None and G is None:
+        raise ValueError("a regularized optimizer_step needs active or G")
+    if reg is not None:
+        G = int(active.numel() if active is not None else G)
     if not _on_gpu(p):
         if active is not None:
             return ref.optimizer_step_masked(
-                kind, p, g, s0, s1, s2, hyper, step, p_lp, active, segments
+                kind, p, g, s0, s1, s2, hyper, step, p_lp, active, segments,
+                reg,
             )
-        return ref.optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp)
+        return ref.optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp,
+                                  reg=reg, table=segments, G=G)
     if step_buf is None:
         raise ValueError("GPU optimizer_step needs a device step_buf")
     h = hyper
     lr = float(h["learning_rate"])
+
+    def masked(code, slots, vals, flag):
+        ext = _require_hip()
+        vals = [float(v) for v in vals]
+        if reg is not None:
+            return ext.optimizer_step_reg(
+                code, p, g, *slots, vals, flag, p_lp, step_buf, active,
+                segments, reg, G,
+            )
+        return ext.optimizer_step_masked(
+            code, p, g, *slots, vals, flag, p_lp, step_buf, active, segments,
+        )
+
+    segment_aware = active is not None or reg is not None
     if kind == "adam" and not h.get("amsgrad"):
-        if active is not None:
-            return _require_hip().optimizer_step_masked(
-                _OPT_ADAM, p, g, s0, s1, None,
-                [lr, float(h["beta_1"]), float(h["beta_2"]),
-                 float(h["epsilon"])],
-                False, p_lp, step_buf, active, segments,
+        if segment_aware:
+            return masked(
+                _OPT_ADAM, (s0, s1, None),
+                [lr, h["beta_1"], h["beta_2"], h["epsilon"]], False,
             )
         return _require_hip().adam_step(
             p, g, s0, s1, lr, float(h["beta_1"]), float(h["beta_2"]),
@@ -281,11 +337,8 @@ def optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp=None,
         vals = [lr, h["beta_1"], h["beta_2"], h["epsilon"]]
     else:
         raise ValueError(f"Unsupported optimizer {kind!r}")
-    if active is not None:
-        return _require_hip().optimizer_step_masked(
-            code, p, g, s0, s1, s2, [float(v) for v in vals], flag, p_lp,
-            step_buf, active, segments,
-        )
+    if segment_aware:
+        return masked(code, (s0, s1, s2), vals, flag)
     return _require_hip().optimizer_step(
         code, p, g, s0, s1, s2, [float(v) for v in vals], flag, p_lp,
         step_buf,

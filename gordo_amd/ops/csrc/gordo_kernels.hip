@@ -574,6 +574,11 @@ __global__ void lstm_pw_bwd_kernel(
 }
 
 // whole-tile weight-grad kernel (wgrad_pipe.hip)
+// the optimizer launch record lives in masked_ops.hip
+namespace gordo_masked {
+void note_optimizer_launch(const char* family, bool reg);
+}
+
 namespace gordo_wgrad {
 constexpr int MSTEP = 32;  // rows of M per step
 bool pipe_shape_ok(int K, int K1, int N);
@@ -878,6 +883,7 @@ void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                      m.data_ptr<float>(), v.data_ptr<float>(), plp_ptr, n,
                      (float)lr, (float)b1, (float)b2, (float)eps,
                      step_buf.data_ptr<int>());
+  gordo_masked::note_optimizer_launch("adam", false);
 }
 
 // launch K<ACT>(args...) for the cell activation code `act`
@@ -1035,12 +1041,31 @@ void remap_models(torch::Tensor dst, torch::Tensor src,
                   std::vector<int64_t> src_index, torch::Tensor dst_table,
                   torch::Tensor src_table, int64_t G_dst, int64_t G_src,
                   c10::optional<torch::Tensor> dst_lp);
+void optimizer_step_reg(int64_t kind, torch::Tensor p, torch::Tensor g,
+                        c10::optional<torch::Tensor> s0,
+                        c10::optional<torch::Tensor> s1,
+                        c10::optional<torch::Tensor> s2,
+                        std::vector<double> hyper, bool flag,
+                        c10::optional<torch::Tensor> plp,
+                        torch::Tensor step_buf,
+                        c10::optional<torch::Tensor> active,
+                        torch::Tensor table, torch::Tensor reg, int64_t G);
+torch::Tensor weight_penalty(torch::Tensor p, torch::Tensor table,
+                             torch::Tensor reg, int64_t G);
+std::tuple<std::string, bool> last_optimizer_launch();
 }  // namespace gordo_masked
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("optimizer_step_masked", &gordo_masked::optimizer_step_masked,
           "optimizer step (every kind, plain Adam = 0) over the models "
           "with active[g] != 0 only");
+  mod.def("optimizer_step_reg", &gordo_masked::optimizer_step_reg,
+          "the masked step with the weight regularizers' gradient term "
+          "fused in (reg: float32 [2, S]; active may be None)");
+  mod.def("weight_penalty", &gordo_masked::weight_penalty,
+          "per-model l1 sum|w| + l2 sum w^2 over the tensors, float32 [G]");
+  mod.def("last_optimizer_launch", &gordo_masked::last_optimizer_launch,
+          "(family, reg) of this thread's last optimizer-step launch");
   mod.def("masked_copy", &gordo_masked::masked_copy, py::arg("dst"),
           py::arg("src"), py::arg("mask"), py::arg("table"),
           py::arg("dst_lp") = py::none(),

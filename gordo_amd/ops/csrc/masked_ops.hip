@@ -9,6 +9,12 @@
 //                          a [G_dst, ...] buffer (+ bf16 mirror), by a
 //                          list of (dst model, src model) pairs: pack
 //                          compaction (see remap_models_kernel)
+//   optimizer_step_reg     the masked step with the weight regularizers'
+//                          gradient term l1 sgn(w) + 2 l2 w fused at the
+//                          gradient load, per tensor (opt_masked_kernel
+//                          <KIND, true>; the mask is optional)
+//   weight_penalty         per-model sum of l1 sum|w| + l2 sum w^2 over
+//                          the tensors (weight_penalty_*_kernel)
 //
 // The flat buffer holds S declared tensors; tensor s is [G, per_s], so
 // model g owns [off_s + g*per_s, off_s + (g+1)*per_s). The segment
@@ -45,6 +51,8 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <string>
+#include <tuple>
 #include <vector>
 
 namespace {
@@ -169,15 +177,15 @@ constexpr int MAX_SEGMENTS = 256;
 // entry and counts the units before it (LDS, 4 arrays of S words); the
 // block then takes units blockIdx.x, blockIdx.x + gridDim.x, ...: the
 // one lane whose segment holds the unit names it, no division and no
-// search. For the unit's element range [lo, hi) of its segment it
-// calls, per lane, vec4(e) for 4 elements at flat index e where the
-// segment moves as 16-byte vectors, else one(e) per element with the
-// block's lanes on consecutive e.
-template <class FV, class FS>
-MK_DEV_INLINE void walk_model_units(const long long* __restrict__ table,
-                                    int S, int g, int G, size_t n,
-                                    size_t n_model, int vec_ok, FV&& vec4,
-                                    FS&& one) {
+// search. For unit u it calls unit(s, base, per, lo, hi, u) in every
+// thread, with block-uniform arguments: the segment's index, the flat
+// index of its slice of model g, its per-model size and the unit's
+// element range [lo, hi) of the slice. The numbering depends on the
+// per_s alone, not on G or on the grid.
+template <class FU>
+MK_DEV_INLINE void walk_units(const long long* __restrict__ table, int S,
+                              int g, int G, size_t n, size_t n_model,
+                              FU&& unit) {
   // lane t < S holds segment t: one round of table loads for the whole
   // block instead of a chain of dependent scalar loads per segment
   __shared__ size_t sh_base[MAX_SEGMENTS], sh_per[MAX_SEGMENTS];
@@ -214,26 +222,126 @@ MK_DEV_INLINE void walk_model_units(const long long* __restrict__ table,
     __syncthreads();  // sh_seg is read: the next round may write it
     const size_t lo = (u - first) << UNIT_SHIFT;
     const size_t hi = lo + UNIT < per ? lo + UNIT : per;
-    if (vec_ok && (per & 3) == 0 && (base & 3) == 0) {
-      const size_t i = lo + ((size_t)threadIdx.x << 2);
-      if (i < hi) vec4(base + i);  // hi % 4 == 0: the 4 are inside
-    } else {
-      for (size_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
-        one(base + i);
-    }
+    unit(s, base, per, lo, hi, u);
   }
 }
 
-template <int KIND>
+// The elements [lo, hi) of one unit: per lane, vec4(e) for 4 elements
+// at flat index e where the segment moves as 16-byte vectors, else
+// one(e) per element with the block's lanes on consecutive e.
+template <class FV, class FS>
+MK_DEV_INLINE void unit_elems(size_t base, size_t per, size_t lo, size_t hi,
+                              int vec_ok, FV&& vec4, FS&& one) {
+  if (vec_ok && (per & 3) == 0 && (base & 3) == 0) {
+    const size_t i = lo + ((size_t)threadIdx.x << 2);
+    if (i < hi) vec4(base + i);  // hi % 4 == 0: the 4 are inside
+  } else {
+    for (size_t i = lo + threadIdx.x; i < hi; i += blockDim.x)
+      one(base + i);
+  }
+}
+
+// walk_units with every unit moved by unit_elems
+template <class FV, class FS>
+MK_DEV_INLINE void walk_model_units(const long long* __restrict__ table,
+                                    int S, int g, int G, size_t n,
+                                    size_t n_model, int vec_ok, FV&& vec4,
+                                    FS&& one) {
+  walk_units(table, S, g, G, n, n_model,
+             [&](int, size_t base, size_t per, size_t lo, size_t hi, size_t) {
+               unit_elems(base, per, lo, hi, vec_ok, vec4, one);
+             });
+}
+
+// The weight regularizer's share of the gradient: a tensor with
+// coefficients (l1, l2) adds l1 sum|w| + l2 sum w^2 to its model's loss,
+// so the optimizer sees gi + (l1 sgn(pi) + (2 l2) pi), sgn(+-0) = 0: a
+// zero-padded entry with a zero gradient stays exactly zero. Products
+// and sums are rounded one by one (no contraction): ops/reference.py
+// repeats this expression.
+MK_DEV_INLINE float reg_grad(float gi, float pi, float l1, float l2x2) {
+#pragma clang fp contract(off)
+  const float sgn = (float)(pi > 0.f) - (float)(pi < 0.f);
+  const float t1 = l1 * sgn;
+  const float t2 = l2x2 * pi;
+  const float r = t1 + t2;
+  return gi + r;
+}
+
+struct StepBufs {
+  float* __restrict__ p;
+  const float* __restrict__ g;
+  float* __restrict__ s0;
+  float* __restrict__ s1;
+  float* __restrict__ s2;
+  bf16* __restrict__ plp;
+  bool use0, use1, use2;
+};
+
+// 4 elements at flat index e; R: with the regularizer term
+template <int KIND, bool R>
+MK_DEV_INLINE void step_vec4(const StepBufs& m, const OptConsts& k, size_t e,
+                             float l1, float l2x2) {
+  float4 gv = *reinterpret_cast<const float4*>(m.g + e);
+  float4 pv = *reinterpret_cast<const float4*>(m.p + e);
+  float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av, cv = av;
+  if (m.use0) av = *reinterpret_cast<const float4*>(m.s0 + e);
+  if (m.use1) bv = *reinterpret_cast<const float4*>(m.s1 + e);
+  if (m.use2) cv = *reinterpret_cast<const float4*>(m.s2 + e);
+  if (R) {
+    gv.x = reg_grad(gv.x, pv.x, l1, l2x2);
+    gv.y = reg_grad(gv.y, pv.y, l1, l2x2);
+    gv.z = reg_grad(gv.z, pv.z, l1, l2x2);
+    gv.w = reg_grad(gv.w, pv.w, l1, l2x2);
+  }
+  opt_elem<KIND>(k, gv.x, pv.x, av.x, bv.x, cv.x);
+  opt_elem<KIND>(k, gv.y, pv.y, av.y, bv.y, cv.y);
+  opt_elem<KIND>(k, gv.z, pv.z, av.z, bv.z, cv.z);
+  opt_elem<KIND>(k, gv.w, pv.w, av.w, bv.w, cv.w);
+  if (m.use0) *reinterpret_cast<float4*>(m.s0 + e) = av;
+  if (m.use1) *reinterpret_cast<float4*>(m.s1 + e) = bv;
+  if (m.use2) *reinterpret_cast<float4*>(m.s2 + e) = cv;
+  *reinterpret_cast<float4*>(m.p + e) = pv;
+  if (m.plp) store_bf16x4(m.plp + e, pv);
+}
+
+template <int KIND, bool R>
+MK_DEV_INLINE void step_one(const StepBufs& m, const OptConsts& k, size_t e,
+                            float l1, float l2x2) {
+  float gi = m.g[e];
+  float pi = m.p[e];
+  float a = 0.f, b = 0.f, c = 0.f;
+  if (m.use0) a = m.s0[e];
+  if (m.use1) b = m.s1[e];
+  if (m.use2) c = m.s2[e];
+  if (R) gi = reg_grad(gi, pi, l1, l2x2);
+  opt_elem<KIND>(k, gi, pi, a, b, c);
+  if (m.use0) m.s0[e] = a;
+  if (m.use1) m.s1[e] = b;
+  if (m.use2) m.s2[e] = c;
+  m.p[e] = pi;
+  if (m.plp) m.plp[e] = f2bf(pi);
+}
+
+// REG: `reg` is the float [2, S] coefficient table beside `table` (row
+// 0 the l1, row 1 the l2 of each tensor) and `active` may be null (no
+// model is frozen). A unit whose segment has both coefficients zero
+// takes the REG = false element code: a block-uniform choice, and the
+// same arithmetic as the plain masked step.
+template <int KIND, bool REG>
 __global__ void opt_masked_kernel(
     float* __restrict__ p, const float* __restrict__ g,
     float* __restrict__ s0, float* __restrict__ s1, float* __restrict__ s2,
     bf16* __restrict__ plp, size_t n, float h0, float h1, float h2, float h3,
     int flag, const int* __restrict__ step_buf,
     const int* __restrict__ active, const long long* __restrict__ table,
-    int S, int vec_ok, size_t n_model) {
+    int S, int vec_ok, size_t n_model, const float* __restrict__ reg) {
   const int mg = blockIdx.y;
-  if (active[mg] == 0) return;
+  if (REG) {
+    if (active != nullptr && active[mg] == 0) return;
+  } else {
+    if (active[mg] == 0) return;
+  }
   OptConsts k;
   k.h0 = h0, k.h1 = h1, k.h2 = h2, k.h3 = h3;
   k.bc1 = 1.f, k.bc2 = 1.f;
@@ -247,44 +355,121 @@ __global__ void opt_masked_kernel(
     k.bc1 = 1.f - powf(h1, fstep);
     k.bc2 = 1.f - powf(h2, fstep);
   }
+  StepBufs m;
+  m.p = p, m.g = g, m.s0 = s0, m.s1 = s1, m.s2 = s2, m.plp = plp;
   // which state slots this kind reads and writes (block-uniform)
-  const bool use0 = KIND != OPT_SGD || h1 != 0.f;
-  const bool use1 = KIND == OPT_ADAM || KIND == OPT_ADAM_AMSGRAD ||
-                    KIND == OPT_ADAMAX || (KIND == OPT_RMSPROP && h2 > 0.f);
-  const bool use2 = KIND == OPT_ADAM_AMSGRAD;
-  walk_model_units(
-      table, S, mg, (int)gridDim.y, n, n_model, vec_ok,
-      [&](size_t e) {
-        float4 gv = *reinterpret_cast<const float4*>(g + e);
-        float4 pv = *reinterpret_cast<const float4*>(p + e);
-        float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av, cv = av;
-        if (use0) av = *reinterpret_cast<const float4*>(s0 + e);
-        if (use1) bv = *reinterpret_cast<const float4*>(s1 + e);
-        if (use2) cv = *reinterpret_cast<const float4*>(s2 + e);
-        opt_elem<KIND>(k, gv.x, pv.x, av.x, bv.x, cv.x);
-        opt_elem<KIND>(k, gv.y, pv.y, av.y, bv.y, cv.y);
-        opt_elem<KIND>(k, gv.z, pv.z, av.z, bv.z, cv.z);
-        opt_elem<KIND>(k, gv.w, pv.w, av.w, bv.w, cv.w);
-        if (use0) *reinterpret_cast<float4*>(s0 + e) = av;
-        if (use1) *reinterpret_cast<float4*>(s1 + e) = bv;
-        if (use2) *reinterpret_cast<float4*>(s2 + e) = cv;
-        *reinterpret_cast<float4*>(p + e) = pv;
-        if (plp) store_bf16x4(plp + e, pv);
-      },
-      [&](size_t e) {
-        float gi = g[e];
-        float pi = p[e];
-        float a = 0.f, b = 0.f, c = 0.f;
-        if (use0) a = s0[e];
-        if (use1) b = s1[e];
-        if (use2) c = s2[e];
-        opt_elem<KIND>(k, gi, pi, a, b, c);
-        if (use0) s0[e] = a;
-        if (use1) s1[e] = b;
-        if (use2) s2[e] = c;
-        p[e] = pi;
-        if (plp) plp[e] = f2bf(pi);
+  m.use0 = KIND != OPT_SGD || h1 != 0.f;
+  m.use1 = KIND == OPT_ADAM || KIND == OPT_ADAM_AMSGRAD ||
+           KIND == OPT_ADAMAX || (KIND == OPT_RMSPROP && h2 > 0.f);
+  m.use2 = KIND == OPT_ADAM_AMSGRAD;
+  walk_units(
+      table, S, mg, (int)gridDim.y, n, n_model,
+      [&](int s, size_t base, size_t per, size_t lo, size_t hi, size_t) {
+        float l1 = 0.f, l2x2 = 0.f;
+        if (REG) {
+          l1 = reg[s];
+          l2x2 = 2.f * reg[S + s];
+        }
+        if (REG && (l1 != 0.f || l2x2 != 0.f)) {
+          unit_elems(
+              base, per, lo, hi, vec_ok,
+              [&](size_t e) { step_vec4<KIND, true>(m, k, e, l1, l2x2); },
+              [&](size_t e) { step_one<KIND, true>(m, k, e, l1, l2x2); });
+        } else {
+          unit_elems(
+              base, per, lo, hi, vec_ok,
+              [&](size_t e) { step_vec4<KIND, false>(m, k, e, 0.f, 0.f); },
+              [&](size_t e) { step_one<KIND, false>(m, k, e, 0.f, 0.f); });
+        }
       });
+}
+
+// Per-model weight penalty, first pass: unit u of model g writes
+// l1 sum|w| + l2 sum w^2 over its elements to part[g * U + u]. A
+// model's bits must not depend on G, on its place in the pack or on
+// the load form (a tensor that is 16-byte aligned in one layout is not
+// in another, and compaction promises a bit-equal fit), so lane t
+// always holds elements lo + 4t .. lo + 4t + 3 of the unit, loaded as
+// one float4 or as four floats (0 past the end), and everything after
+// the load is one piece of code: pairwise in the lane, a xor butterfly
+// over the wave's 64 lanes, the 4 waves' sums pairwise through LDS. No
+// atomics. A segment with both coefficients zero is not read: its
+// units write 0.
+__global__ void weight_penalty_units_kernel(
+    const float* __restrict__ p, size_t n, const long long* __restrict__ table,
+    const float* __restrict__ reg, int S, int vec_ok, size_t n_model,
+    float* __restrict__ part, size_t U) {
+  __shared__ float sh_a[4], sh_q[4];
+  const int mg = blockIdx.y;
+  const int t = threadIdx.x;
+  walk_units(
+      table, S, mg, (int)gridDim.y, n, n_model,
+      [&](int s, size_t base, size_t per, size_t lo, size_t hi, size_t u) {
+        const float l1 = reg[s], l2 = reg[S + s];
+        float x0 = 0.f, x1 = 0.f, x2 = 0.f, x3 = 0.f;
+        if (l1 != 0.f || l2 != 0.f) {  // block-uniform
+          const size_t i = lo + ((size_t)t << 2);
+          if (vec_ok && (per & 3) == 0 && (base & 3) == 0) {
+            if (i < hi) {  // hi % 4 == 0: the 4 are inside
+              float4 v = *reinterpret_cast<const float4*>(p + base + i);
+              x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
+            }
+          } else {
+            if (i < hi) x0 = p[base + i];
+            if (i + 1 < hi) x1 = p[base + i + 1];
+            if (i + 2 < hi) x2 = p[base + i + 2];
+            if (i + 3 < hi) x3 = p[base + i + 3];
+          }
+        }
+        float a, q;
+        {
+#pragma clang fp contract(off)
+          a = (fabsf(x0) + fabsf(x1)) + (fabsf(x2) + fabsf(x3));
+          q = (x0 * x0 + x1 * x1) + (x2 * x2 + x3 * x3);
+        }
+        for (int d = 32; d >= 1; d >>= 1) {
+          a += __shfl_xor(a, d, 64);
+          q += __shfl_xor(q, d, 64);
+        }
+        if ((t & 63) == 0) {
+          sh_a[t >> 6] = a;
+          sh_q[t >> 6] = q;
+        }
+        __syncthreads();
+        if (t == 0 && u < U) {
+#pragma clang fp contract(off)
+          const float A = (sh_a[0] + sh_a[1]) + (sh_a[2] + sh_a[3]);
+          const float Q = (sh_q[0] + sh_q[1]) + (sh_q[2] + sh_q[3]);
+          const float ta = l1 * A;
+          const float tq = l2 * Q;
+          part[(size_t)mg * U + u] = ta + tq;
+        }
+        __syncthreads();  // sh_a / sh_q are read: the next unit writes
+      });
+}
+
+// Second pass: one wave per model sums its units' partials, lane j
+// units j, j + 64, ... in that order, then the same xor butterfly. The
+// number of units follows from the per_s alone (counted as walk_units
+// counts them), so the result does not depend on G or on the grid.
+__global__ void weight_penalty_sum_kernel(
+    const float* __restrict__ part, size_t U,
+    const long long* __restrict__ table, int S, int G, size_t n,
+    size_t n_model, float* __restrict__ out) {
+  const int mg = blockIdx.x;
+  const int t = threadIdx.x;  // 64 threads
+  unsigned long long units = 0;
+  for (int s = t; s < S; s += 64) {
+    size_t base = 0, per = 0;
+    if (segment_slice(table, S, s, mg, G, n, n_model, base, per))
+      units += (per + UNIT - 1) >> UNIT_SHIFT;
+  }
+  for (int d = 32; d >= 1; d >>= 1) units += __shfl_xor(units, d, 64);
+  const size_t total = units < U ? (size_t)units : U;
+  float acc = 0.f;
+  for (size_t u = t; u < total; u += 64) acc += part[(size_t)mg * U + u];
+  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  if (t == 0) out[mg] = acc;
 }
 
 __global__ void masked_copy_kernel(float* __restrict__ dst,
@@ -414,6 +599,21 @@ hipStream_t cur_stream() {
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// [2, S] int64 table on p's device; returns S
+int check_table(const torch::Tensor& p, const torch::Tensor& table) {
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == torch::kInt64 &&
+                  table.is_contiguous() && table.dim() == 2 &&
+                  table.size(0) == 2,
+              "the segment table must be a contiguous int64 [2, S] GPU "
+              "tensor");
+  TORCH_CHECK(table.get_device() == p.get_device(),
+              "mask and segment table must live on the buffer's device");
+  int64_t S = table.size(1);
+  TORCH_CHECK(S >= 1 && S <= MAX_SEGMENTS, "the segment table holds ", S,
+              " tensors; the masked kernels take 1 to ", MAX_SEGMENTS);
+  return (int)S;
+}
+
 // [G] int32 mask and [2, S] int64 table on p's device; returns (G, S)
 std::pair<int, int> check_mask_table(const torch::Tensor& p,
                                      const torch::Tensor& mask,
@@ -421,20 +621,32 @@ std::pair<int, int> check_mask_table(const torch::Tensor& p,
   TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kInt32 &&
                   mask.is_contiguous() && mask.dim() == 1,
               "the model mask must be a contiguous int32 [G] GPU tensor");
-  TORCH_CHECK(table.is_cuda() && table.scalar_type() == torch::kInt64 &&
-                  table.is_contiguous() && table.dim() == 2 &&
-                  table.size(0) == 2,
-              "the segment table must be a contiguous int64 [2, S] GPU "
-              "tensor");
-  TORCH_CHECK(mask.get_device() == p.get_device() &&
-                  table.get_device() == p.get_device(),
+  TORCH_CHECK(mask.get_device() == p.get_device(),
               "mask and segment table must live on the buffer's device");
-  int64_t G = mask.numel(), S = table.size(1);
+  int S = check_table(p, table);
+  int64_t G = mask.numel();
   TORCH_CHECK(G >= 1 && G <= 65535, "G must be in [1, 65535]");
-  TORCH_CHECK(S >= 1 && S <= MAX_SEGMENTS, "the segment table holds ", S,
-              " tensors; the masked kernels take 1 to ", MAX_SEGMENTS);
-  return {(int)G, (int)S};
+  return {(int)G, S};
 }
+
+// float32 [2, S] coefficient table beside the segment table
+const float* check_reg(const torch::Tensor& p, const torch::Tensor& reg,
+                       int S) {
+  TORCH_CHECK(reg.is_cuda() && reg.scalar_type() == torch::kFloat32 &&
+                  reg.is_contiguous() && reg.dim() == 2 &&
+                  reg.size(0) == 2 && reg.size(1) == S &&
+                  reg.get_device() == p.get_device(),
+              "the regularizer table must be a contiguous float32 [2, S] "
+              "tensor on the buffer's device, S that of the segment table");
+  return reg.data_ptr<float>();
+}
+
+// which optimizer kernel this thread launched last
+struct OptLaunch {
+  const char* family = "";
+  bool reg = false;
+};
+thread_local OptLaunch g_last_opt;
 
 // blocks per model: one per work unit -- a model has at most
 // n/G/1024 + S units (each segment's last unit may be partial) --
@@ -450,14 +662,27 @@ int chunks_for(size_t n, int G, int S) {
 
 namespace gordo_masked {
 
-void optimizer_step_masked(int64_t kind, torch::Tensor p, torch::Tensor g,
-                           c10::optional<torch::Tensor> s0,
-                           c10::optional<torch::Tensor> s1,
-                           c10::optional<torch::Tensor> s2,
-                           std::vector<double> hyper, bool flag,
-                           c10::optional<torch::Tensor> plp,
-                           torch::Tensor step_buf, torch::Tensor active,
-                           torch::Tensor table) {
+void note_optimizer_launch(const char* family, bool reg) {
+  g_last_opt.family = family;
+  g_last_opt.reg = reg;
+}
+
+std::tuple<std::string, bool> last_optimizer_launch() {
+  return {std::string(g_last_opt.family), g_last_opt.reg};
+}
+
+// the masked step (active, no reg), the regularized step (reg, with or
+// without active; G then comes from the caller) or both
+static void masked_step_impl(int64_t kind, torch::Tensor p, torch::Tensor g,
+                             c10::optional<torch::Tensor> s0,
+                             c10::optional<torch::Tensor> s1,
+                             c10::optional<torch::Tensor> s2,
+                             std::vector<double> hyper, bool flag,
+                             c10::optional<torch::Tensor> plp,
+                             torch::Tensor step_buf,
+                             c10::optional<torch::Tensor> active,
+                             torch::Tensor table,
+                             c10::optional<torch::Tensor> reg, int64_t G_arg) {
   TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
                   p.is_contiguous(),
               "p must be a contiguous fp32 GPU tensor");
@@ -467,8 +692,21 @@ void optimizer_step_masked(int64_t kind, torch::Tensor p, torch::Tensor g,
   TORCH_CHECK(step_buf.is_cuda() && step_buf.scalar_type() == torch::kInt32,
               "step_buf must be an int32 GPU tensor");
   TORCH_CHECK(hyper.size() == 4, "hyper must hold 4 values");
-  auto gs = check_mask_table(p, active, table);
-  int G = gs.first, S = gs.second;
+  int G, S;
+  const int* active_ptr = nullptr;
+  if (active.has_value()) {
+    auto gs = check_mask_table(p, *active, table);
+    G = gs.first, S = gs.second;
+    TORCH_CHECK(G_arg <= 0 || G_arg == G, "the mask holds ", G,
+                " models, G is ", G_arg);
+    active_ptr = active->data_ptr<int>();
+  } else {
+    TORCH_CHECK(reg.has_value(), "a step without a mask needs reg");
+    TORCH_CHECK(G_arg >= 1 && G_arg <= 65535, "G must be in [1, 65535]");
+    G = (int)G_arg;
+    S = check_table(p, table);
+  }
+  const float* reg_ptr = reg.has_value() ? check_reg(p, *reg, S) : nullptr;
   size_t n = p.numel();
   bool vec = aligned16(p.data_ptr()) && aligned16(g.data_ptr());
   auto slot = [&](const c10::optional<torch::Tensor>& s, bool needed,
@@ -521,16 +759,24 @@ void optimizer_step_masked(int64_t kind, torch::Tensor p, torch::Tensor g,
   }
   hipLaunchKernelGGL(masked_bump_kernel, dim3(1), dim3(64), 0, cur_stream(),
                      step_buf.data_ptr<int>());
+  note_optimizer_launch("masked", reg_ptr != nullptr);
   if (n == 0) return;
   TORCH_CHECK(n % (size_t)G == 0, "buffer size must be a multiple of G");
   int chunks = chunks_for(n, G, S);
-#define GORDO_MASKED_LAUNCH(K)                                               \
-  hipLaunchKernelGGL(opt_masked_kernel<K>, dim3(chunks, G), dim3(256), 0,    \
-                     cur_stream(), p.data_ptr<float>(), g.data_ptr<float>(), \
-                     a, b, c, plp_ptr, n, h0, h1, h2, h3, flag ? 1 : 0,      \
-                     step_buf.data_ptr<int>(), active.data_ptr<int>(),       \
+#define GORDO_MASKED_LAUNCH_R(K, R)                                          \
+  hipLaunchKernelGGL((opt_masked_kernel<K, R>), dim3(chunks, G), dim3(256),  \
+                     0, cur_stream(), p.data_ptr<float>(),                   \
+                     g.data_ptr<float>(), a, b, c, plp_ptr, n, h0, h1, h2,   \
+                     h3, flag ? 1 : 0, step_buf.data_ptr<int>(), active_ptr, \
                      (const long long*)table.data_ptr<int64_t>(), S,         \
-                     vec ? 1 : 0, n / (size_t)G)
+                     vec ? 1 : 0, n / (size_t)G, reg_ptr)
+#define GORDO_MASKED_LAUNCH(K)              \
+  do {                                      \
+    if (reg_ptr)                            \
+      GORDO_MASKED_LAUNCH_R(K, true);       \
+    else                                    \
+      GORDO_MASKED_LAUNCH_R(K, false);      \
+  } while (0)
   switch (kind) {
     case OPT_ADAM: GORDO_MASKED_LAUNCH(OPT_ADAM); break;
     case OPT_SGD: GORDO_MASKED_LAUNCH(OPT_SGD); break;
@@ -540,6 +786,68 @@ void optimizer_step_masked(int64_t kind, torch::Tensor p, torch::Tensor g,
     default: GORDO_MASKED_LAUNCH(OPT_ADAMAX); break;
   }
 #undef GORDO_MASKED_LAUNCH
+#undef GORDO_MASKED_LAUNCH_R
+}
+
+void optimizer_step_masked(int64_t kind, torch::Tensor p, torch::Tensor g,
+                           c10::optional<torch::Tensor> s0,
+                           c10::optional<torch::Tensor> s1,
+                           c10::optional<torch::Tensor> s2,
+                           std::vector<double> hyper, bool flag,
+                           c10::optional<torch::Tensor> plp,
+                           torch::Tensor step_buf, torch::Tensor active,
+                           torch::Tensor table) {
+  masked_step_impl(kind, p, g, s0, s1, s2, hyper, flag, plp, step_buf, active,
+                   table, c10::nullopt, 0);
+}
+
+// The segment-aware step with the weight regularizers' gradient term
+// fused at the gradient load: `reg` is the float32 [2, S] coefficient
+// table (l1 row, l2 row). `active` is optional: without it every one
+// of the G models steps.
+void optimizer_step_reg(int64_t kind, torch::Tensor p, torch::Tensor g,
+                        c10::optional<torch::Tensor> s0,
+                        c10::optional<torch::Tensor> s1,
+                        c10::optional<torch::Tensor> s2,
+                        std::vector<double> hyper, bool flag,
+                        c10::optional<torch::Tensor> plp,
+                        torch::Tensor step_buf,
+                        c10::optional<torch::Tensor> active,
+                        torch::Tensor table, torch::Tensor reg, int64_t G) {
+  masked_step_impl(kind, p, g, s0, s1, s2, hyper, flag, plp, step_buf, active,
+                   table, reg, G);
+}
+
+// Per-model penalty sum_s (l1_s sum|w_s| + l2_s sum w_s^2) of the flat
+// buffer p, float32 [G]; reads p only (see the two kernels).
+torch::Tensor weight_penalty(torch::Tensor p, torch::Tensor table,
+                             torch::Tensor reg, int64_t G) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
+                  p.is_contiguous(),
+              "p must be a contiguous fp32 GPU tensor");
+  TORCH_CHECK(G >= 1 && G <= 65535, "G must be in [1, 65535]");
+  int S = check_table(p, table);
+  const float* reg_ptr = check_reg(p, reg, S);
+  size_t n = p.numel();
+  auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(p.device());
+  if (n == 0) return torch::zeros({G}, opts);
+  TORCH_CHECK(n % (size_t)G == 0, "buffer size must be a multiple of G");
+  size_t n_model = n / (size_t)G;
+  // a model has at most n/G/1024 + S units (chunks_for); a table whose
+  // segments overlap could name more, and those are dropped
+  size_t U = (n_model >> UNIT_SHIFT) + (size_t)S;
+  auto part = torch::empty({G, (int64_t)U}, opts);
+  auto out = torch::empty({G}, opts);
+  int chunks = chunks_for(n, (int)G, S);
+  const long long* tab = (const long long*)table.data_ptr<int64_t>();
+  hipLaunchKernelGGL(weight_penalty_units_kernel, dim3(chunks, (unsigned)G),
+                     dim3(256), 0, cur_stream(), p.data_ptr<float>(), n, tab,
+                     reg_ptr, S, aligned16(p.data_ptr()) ? 1 : 0, n_model,
+                     part.data_ptr<float>(), U);
+  hipLaunchKernelGGL(weight_penalty_sum_kernel, dim3((unsigned)G), dim3(64),
+                     0, cur_stream(), part.data_ptr<float>(), U, tab, S,
+                     (int)G, n, n_model, out.data_ptr<float>());
+  return out;
 }
 
 void masked_copy(torch::Tensor dst, torch::Tensor src, torch::Tensor mask,

@@ -200,13 +200,21 @@ def optimizer_step(
     hyper: dict,
     step: int,
     p_lp: Optional[torch.Tensor] = None,
+    reg: Optional[torch.Tensor] = None,
+    table: Optional[torch.Tensor] = None,
+    G: Optional[int] = None,
 ):
     """One in-place optimizer step over a flat fp32 parameter buffer
     (Keras 3 update rules); refreshes the low-precision mirror when
     given. ``kind`` is the spec's canonical optimizer name, ``hyper``
     its complete ``optimizer_params``; s0/s1/s2 are the state slots
     (m / v / v̂ for Adam; momentum for SGD; v + momentum for RMSprop;
-    the accumulator for Adagrad; m / u for Adamax)."""
+    the accumulator for Adagrad; m / u for Adamax). With ``reg`` (the
+    float32 [2, S] coefficient table beside the segment ``table`` of a
+    buffer of ``G`` models) the step sees ``regularized_grad`` instead
+    of ``g``; ``g`` itself is not modified."""
+    if reg is not None:
+        g = regularized_grad(p, g, table, reg, G)
     lr = float(hyper["learning_rate"])
     if kind == "adam" and not hyper.get("amsgrad"):
         adam_step(p, g, s0, s1, lr, hyper["beta_1"], hyper["beta_2"],
@@ -378,6 +386,61 @@ def remap_models(
             )
 
 
+def reg_table(l1, l2, device=None) -> torch.Tensor:
+    """The float32 [2, S] regularizer table that goes with a segment
+    table: row 0 the l1, row 1 the l2 coefficient of each tensor."""
+    return torch.tensor(
+        [[float(a) for a in l1], [float(b) for b in l2]],
+        dtype=torch.float32, device=device,
+    ).reshape(2, -1)
+
+
+def _reg_segments(table: torch.Tensor, reg: torch.Tensor, n: int, G: int):
+    """(offset, per-model size, l1, l2) of every tensor with a non-zero
+    coefficient whose table entry fits into the n-element buffer (the
+    kernels skip the others too)."""
+    offs, pers = table.tolist()
+    l1s, l2s = reg.tolist()
+    for off, per, l1, l2 in zip(offs, pers, l1s, l2s):
+        if off < 0 or per <= 0 or off + per * G > n:
+            continue
+        if l1 != 0.0 or l2 != 0.0:
+            yield off, per, l1, l2
+
+
+def regularized_grad(p, g, table, reg, G: int) -> torch.Tensor:
+    """What the optimizer sees under weight regularizers: for a tensor
+    with coefficients (l1, l2), ``g + (l1 sgn(p) + (2 l2) p)`` with
+    ``sgn(±0) = 0``, every product and sum rounded on its own (the
+    expression of ``reg_grad`` in masked_ops.hip); ``g`` unchanged for
+    the other tensors. A new tensor of ``g``'s dtype."""
+    out = g.clone()
+    dt = g.dtype
+    for off, per, l1, l2 in _reg_segments(table, reg, p.numel(), int(G)):
+        sl = slice(off, off + int(G) * per)
+        pi = p[sl].to(dt)
+        t1 = torch.tensor(l1, dtype=dt) * torch.sign(pi)
+        t2 = torch.tensor(2.0 * l2, dtype=dt) * pi
+        out[sl] = g[sl] + (t1 + t2)
+    return out
+
+
+def weight_penalty(p, table, reg, G: int) -> torch.Tensor:
+    """Per-model ``sum_s (l1_s sum|w_s| + l2_s sum w_s^2)`` of the flat
+    buffer ``p``, float32 [G] (Keras adds this to the model's loss).
+    CPU form of the HIP ``weight_penalty``: fp32 throughout, torch's
+    own summation order."""
+    G = int(G)
+    out = torch.zeros(G, dtype=torch.float32, device=p.device)
+    for off, per, l1, l2 in _reg_segments(table, reg, p.numel(), G):
+        w = p[off : off + G * per].view(G, per).to(torch.float32)
+        out += (
+            torch.tensor(l1, dtype=torch.float32) * w.abs().sum(dim=1)
+            + torch.tensor(l2, dtype=torch.float32) * (w * w).sum(dim=1)
+        )
+    return out
+
+
 def optimizer_step_masked(
     kind: str,
     p: torch.Tensor,
@@ -390,6 +453,7 @@ def optimizer_step_masked(
     p_lp: Optional[torch.Tensor],
     active: torch.Tensor,
     table: torch.Tensor,
+    reg: Optional[torch.Tensor] = None,
 ):
     """``optimizer_step`` for the models with ``active[g] != 0`` only:
     the parameters, state slots and mirror of every other model keep
@@ -399,7 +463,8 @@ def optimizer_step_masked(
     frozen = (active.reshape(-1) == 0).to(torch.int32)
     bufs = [t for t in (p, s0, s1, s2, p_lp) if t is not None]
     saved = [t.clone() for t in bufs] if bool(frozen.any()) else []
-    optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp)
+    optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp, reg=reg,
+                   table=table, G=active.numel())
     for t, keep in zip(bufs, saved):
         for (rows, d), (_, s) in zip(
             _model_slices(t, frozen, table), _model_slices(keep, frozen, table)
@@ -926,5 +991,64 @@ def adam_step_ref(p, g, m, v, lr, beta1, beta2, eps, step):
         lr_t = torch.tensor(lr, dtype=dt)
         p1 = p.to(dt) - lr_t / bc1 * m1 / (torch.sqrt(v1 / bc2) + eps)
         return p1, m1, v1
+
+    return _both(run)
+
+
+def reg_step_ref(kind, p, g, s0, s1, s2, hyper, step, table, reg, G):
+    """One optimizer step of any kind under weight regularizers, out of
+    place: the gradient term ``l1 sgn(p) + 2 l2 p`` (``sgn(±0) = 0``)
+    of each tensor's coefficients is added to ``g`` and the Keras rule
+    of ``optimizer_step`` follows. ``hyper``'s values and the
+    coefficients are taken as the fp32 values the kernel receives.
+    Returns ``((p, s0, s1, s2) fp64, (...) fp32)``; a slot the caller
+    passes as None comes back as None."""
+    h32 = {
+        k: (v if isinstance(v, bool)
+            else float(torch.tensor(float(v), dtype=torch.float32)))
+        for k, v in hyper.items()
+    }
+
+    def run(dt):
+        pp = p.detach().cpu().to(dt, copy=True)
+        gg = g.detach().cpu().to(dt)
+        slots = [None if s is None else s.detach().cpu().to(dt, copy=True)
+                 for s in (s0, s1, s2)]
+        optimizer_step(kind, pp, gg, *slots, h32, int(step), None,
+                       reg=reg.cpu(), table=table.cpu(), G=int(G))
+        return (pp, *slots)
+
+    return _both(run)
+
+
+def weight_penalty_ref(p, table, reg, G):
+    """Per-model ``sum_s (l1_s sum|w_s| + l2_s sum w_s^2)``, [G]:
+    ``(fp64, fp32)``. The fp32 value sums each tensor left to right in
+    fp32 (numpy ``add.accumulate``, as ``mse_bwd_ref``): the order-free
+    worst case that a reduction tree improves on."""
+    import numpy as np
+
+    G = int(G)
+    p = p.detach().cpu()
+    segs = list(_reg_segments(table.cpu(), reg.cpu(), p.numel(), G))
+
+    def run(dt):
+        out = torch.zeros(G, dtype=dt)
+        for off, per, l1, l2 in segs:
+            w = p[off : off + G * per].view(G, per).to(dt)
+            a, q = w.abs(), w * w
+            if dt == torch.float32:
+                a, q = (
+                    torch.from_numpy(
+                        np.add.accumulate(t.numpy(), axis=1,
+                                          dtype=np.float32)[:, -1].copy()
+                    )
+                    for t in (a, q)
+                )
+            else:
+                a, q = a.sum(dim=1), q.sum(dim=1)
+            out = out + (torch.tensor(l1, dtype=dt) * a
+                         + torch.tensor(l2, dtype=dt) * q)
+        return out
 
     return _both(run)
