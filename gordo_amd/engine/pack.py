@@ -1230,133 +1230,90 @@ class LSTMPack(BasePack):
             self.store.views["Wd"][g][:fin_l, :fout_l].copy_(wd)
 
     # ---- sequence forward/backward ------------------------------------
-    def _use_fused(self, B: Optional[int] = None) -> bool:
-        """The fused on-device sequence-scan kernels (lstm_seq.hip) run
-        the whole T-step recurrence in one launch per layer (Wh in LDS
-        for H<=64, streamed from L2 for 64<H<=256). Used on GPU when
-        every layer has a fused kernel AND — for big-H stacks — the
-        scan grid fills the chip: the round-2 GPU A/B at dims
-        256/128/64 measured fused 14% SLOWER at G=16 (128 workgroups on
-        256 CUs) and 7% faster at G=64 (512 WGs), so stacks with H>64
-        take the fused path only when G*ceil(B/32) >= 256 (the
-        per-timestep grouped-GEMM fallback splits the gate columns over
-        many more workgroups and wins in the underfilled regime)."""
+    def _scan_modes(self, B: Optional[int] = None) -> List[str]:
+        """How each layer runs, as the scan planner answers
+        (``ops.lstm_layer_mode``): "fused" (one scan launch per layer
+        and direction, the x-side GEMM inside it), "two_step" (x-GEMM,
+        then one scan launch) or "per_step" (per-timestep kernels). A
+        stack runs the scans only when every layer has one — and, for
+        big-H stacks, the scan grid fills the chip: the round-2 GPU A/B
+        at dims 256/128/64 measured fused 14% SLOWER at G=16 (128
+        workgroups on 256 CUs) and 7% faster at G=64 (512 WGs) — so one
+        per_step layer sends the whole stack per timestep."""
+        n = len(self.lstm_meta)
         if self.device.type != "cuda":
-            return False
-        if not all(
-            ops.lstm_seq_available(H) for _fin, H, _rs in self.lstm_meta
-        ):
-            return False
-        # only the v4 forward / pipelined backward kernels take a cell
-        # activation; otherwise the whole stack runs per timestep
-        # through the activation-aware pointwise kernels
-        if not all(
-            act == "tanh" or ops.lstm_act_scan_available(H, fin)
+            return ["per_step"] * n
+        rows = B if B is not None else 256
+        modes = [
+            ops.lstm_layer_mode(self.G, rows, H, fin, act)
             for (fin, H, _rs), act in zip(self.lstm_meta, self.lstm_acts)
-        ):
-            return False
-        if any(H > 64 for _fin, H, _rs in self.lstm_meta):
-            rows = B if B is not None else 256
-            if self.G * ((rows + 31) // 32) < 256:
-                return False
-        return True
+        ]
+        return ["per_step"] * n if "per_step" in modes else modes
 
-    def _forward_seq(self, Xw: torch.Tensor, keep: bool):
-        """Xw: [G, B, T, F]. Returns (y, cache)."""
-        G, B, T, _ = Xw.shape
-        if self._use_fused(B):
-            return self._forward_seq_fused(Xw, keep)
+    def _use_fused(self, B: Optional[int] = None) -> bool:
+        return "per_step" not in self._scan_modes(B)
+
+    def _layer_fwd_steps(self, li, seq, keep):
+        """One layer per timestep: x-GEMM, then T x (h@Wh, gate math)."""
+        G, B, T, fin = seq.shape
+        H = self.lstm_meta[li][1]
+        Wx = self.store.cviews[f"Wx{li}"]
+        Wh = self.store.cviews[f"Wh{li}"]
+        b = self.store.views[f"bl{li}"]
+        gates_all = ops.grouped_linear_fwd(
+            seq.reshape(G, B * T, fin), Wx, b, "linear"
+        ).view(G, B, T, 4 * H)
+        lp = dict(dtype=self.compute_dtype, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        h = torch.zeros(G, B, H, **lp)
+        c = torch.zeros(G, B, H, **f32)
+        hs = torch.empty(G, B, T, H, **lp)
+        cs = torch.empty(G, B, T, H, **f32) if keep else None
+        gacts = torch.empty(G, B, T, 4 * H, **lp) if keep else None
+        for t in range(T):
+            gates = gates_all[:, :, t].contiguous()
+            ops.grouped_gemm_acc(h, Wh, gates)
+            h, c, gact = ops.lstm_pointwise_fwd(gates, c, self.lstm_acts[li])
+            hs[:, :, t] = h
+            if keep:
+                cs[:, :, t] = c
+                gacts[:, :, t] = gact
+        return hs, cs, gacts
+
+    def _layer_fwd_scan(self, li, mode, seq, keep):
+        """One layer in one scan launch. "fused" computes the x-side
+        gate GEMM INSIDE the scan (no xW HBM round trip — the fleet's
+        scans are bandwidth-bound) and skips the cs/gacts stores on
+        inference passes; "two_step" runs the x-GEMM, then the scan."""
+        G, B, T, fin = seq.shape
+        H = self.lstm_meta[li][1]
+        Wx = self.store.cviews[f"Wx{li}"]
+        Wh = self.store.cviews[f"Wh{li}"]
+        b = self.store.views[f"bl{li}"]
+        if mode == "fused":
+            out = ops.lstm_seq_fwd_fused(seq, Wx, Wh, b, store_aux=keep,
+                                         act=self.lstm_acts[li])
+            return (out[0], out[1], out[2]) if keep else (out[0], None, None)
+        xW = ops.grouped_linear_fwd(
+            seq.reshape(G, B * T, fin), Wx, b, "linear"
+        ).view(G, B, T, 4 * H)
+        hs, cs, gacts = ops.lstm_seq_fwd(xW, Wh)
+        return (hs, cs, gacts) if keep else (hs, None, None)
+
+    def _forward_seq(self, Xw: torch.Tensor, keep: bool, modes=None):
+        """Xw: [G, B, T, F]. Returns (y, cache). ``modes``: the answer
+        of ``_scan_modes`` where the caller already has it."""
+        if modes is None:
+            modes = self._scan_modes(Xw.shape[1])
         seq = Xw
         cache = []
-        for li, (fin, H, rs) in enumerate(self.lstm_meta):
-            Wx = self.store.cviews[f"Wx{li}"]
-            Wh = self.store.cviews[f"Wh{li}"]
-            b = self.store.views[f"bl{li}"]
-            flat_in = seq.reshape(G, B * T, fin)
-            gates_all = ops.grouped_linear_fwd(flat_in, Wx, b, "linear").view(
-                G, B, T, 4 * H
-            )
-            h = torch.zeros(G, B, H, dtype=self.compute_dtype, device=self.device)
-            c = torch.zeros(G, B, H, dtype=torch.float32, device=self.device)
-            hs = torch.empty(
-                G, B, T, H, dtype=self.compute_dtype, device=self.device
-            )
-            cs = (
-                torch.empty(G, B, T, H, dtype=torch.float32, device=self.device)
-                if keep
-                else None
-            )
-            gacts = (
-                torch.empty(
-                    G, B, T, 4 * H, dtype=self.compute_dtype, device=self.device
-                )
-                if keep
-                else None
-            )
-            for t in range(T):
-                gates = gates_all[:, :, t].contiguous()
-                ops.grouped_gemm_acc(h, Wh, gates)
-                h, c, gact = ops.lstm_pointwise_fwd(
-                    gates, c, self.lstm_acts[li]
-                )
-                hs[:, :, t] = h
-                if keep:
-                    cs[:, :, t] = c
-                    gacts[:, :, t] = gact
+        for li, mode in enumerate(modes):
+            if mode == "per_step":
+                hs, cs, gacts = self._layer_fwd_steps(li, seq, keep)
+            else:
+                hs, cs, gacts = self._layer_fwd_scan(li, mode, seq, keep)
             cache.append(
                 dict(seq_in=seq if keep else None, hs=hs, cs=cs, gacts=gacts)
-            )
-            seq = hs
-        h_last = seq[:, :, -1].contiguous()
-        fin, fout, act = self.dense_meta
-        y = ops.grouped_linear_fwd(
-            h_last, self.store.cviews["Wd"], self.store.views["bd"], act
-        )
-        if keep:
-            cache.append(dict(h_last=h_last, y=y))
-        return y, cache
-
-    def _forward_seq_fused(self, Xw: torch.Tensor, keep: bool):
-        """GPU path: one fused scan per layer. Layers fitting the v4
-        geometry compute the x-side gate GEMM INSIDE the scan (no xW
-        HBM round trip — the fleet's scans are bandwidth-bound) and
-        skip the cs/gacts stores on inference passes; other layers use
-        the two-step x-GEMM + scan."""
-        import os as _os
-
-        G, B, T, _ = Xw.shape
-        v4_on = _os.environ.get("GORDO_LSTM_V4", "1") != "0"
-        seq = Xw
-        cache = []
-        for li, (fin, H, rs) in enumerate(self.lstm_meta):
-            Wx = self.store.cviews[f"Wx{li}"]
-            Wh = self.store.cviews[f"Wh{li}"]
-            b = self.store.views[f"bl{li}"]
-            act = self.lstm_acts[li]
-            if v4_on and ops.lstm_v4_available(H, fin):
-                out = ops.lstm_seq_fwd_fused(seq, Wx, Wh, b,
-                                             store_aux=keep, act=act)
-                hs = out[0]
-                cs = out[1] if keep else None
-                gacts = out[2] if keep else None
-            else:
-                if act != "tanh":  # _use_fused keeps such stacks out
-                    raise RuntimeError(
-                        f"no fused forward scan for LSTM activation {act!r}"
-                    )
-                xW = ops.grouped_linear_fwd(
-                    seq.reshape(G, B * T, fin), Wx, b, "linear"
-                ).view(G, B, T, 4 * H)
-                hs, cs, gacts = ops.lstm_seq_fwd(xW, Wh)
-                if not keep:
-                    cs = gacts = None
-            cache.append(
-                dict(
-                    seq_in=seq if keep else None,
-                    hs=hs,
-                    cs=cs,
-                    gacts=gacts,
-                )
             )
             seq = hs
         h_last = seq[:, :, -1].contiguous()
@@ -1381,59 +1338,90 @@ class LSTMPack(BasePack):
         loss, _, correct = self._loss_bwd(y, Tb, want_grad=False)
         return loss, correct
 
-    def _train_batch_fused(self, Xw, Tb) -> torch.Tensor:
-        G, B, T, _ = Xw.shape
-        y, cache = self._forward_seq_fused(Xw, keep=True)
-        loss, dY, self.last_correct = self._loss_bwd(y, Tb)
-
+    def _head_bwd(self, head, dY):
+        """Output dense layer backward: stores dWd / dbd, returns the
+        gradient on the last hidden state."""
         fin, fout, act = self.dense_meta
-        head = cache[-1]
         dZ = ops.act_l1_bwd(dY, head["y"], act, 0.0)
         dWd, dbd = ops.grouped_linear_wgrad(head["h_last"], dZ)
         self.store.gviews["Wd"].copy_(dWd)
         self.store.gviews["bd"].copy_(dbd)
-        dh_last = ops.grouped_linear_bwd_data(dZ, self.store.cviews["Wd"])
+        return ops.grouped_linear_bwd_data(dZ, self.store.cviews["Wd"])
 
-        import os as _os
+    def _layer_bwd_steps(self, li, lc, d_in, last_only):
+        """BPTT through one layer per timestep: returns dG [G,B,T,4H]."""
+        cs, gacts = lc["cs"], lc["gacts"]
+        G, B, T, H = cs.shape
+        Wh = self.store.cviews[f"Wh{li}"]
+        lp = dict(dtype=self.compute_dtype, device=self.device)
+        dG = torch.empty(G, B, T, 4 * H, **lp)
+        dh_carry = torch.zeros(G, B, H, **lp)
+        dc_carry = torch.zeros(G, B, H, dtype=torch.float32, device=self.device)
+        for t in range(T - 1, -1, -1):
+            dh_t = dh_carry
+            if not last_only:
+                dh_t = dh_t + d_in[:, :, t]
+            elif t == T - 1:
+                dh_t = dh_t + d_in
+            c_prev = cs[:, :, t - 1] if t > 0 else torch.zeros_like(dc_carry)
+            dgates, dc_carry = ops.lstm_pointwise_bwd(
+                dh_t, dc_carry, gacts[:, :, t], cs[:, :, t], c_prev,
+                self.lstm_acts[li],
+            )
+            dG[:, :, t] = dgates
+            dh_carry = ops.grouped_linear_bwd_data(dgates, Wh)
+        return dG
 
-        v5_on = _os.environ.get("GORDO_LSTM_V4", "1") != "0"
-        dSeq = None
+    def _store_layer_grads(self, li, lc, dG_flat, T):
+        """Batched weight grads over all (B, T) rows, in one combined
+        pass: dZ (dG) staged once for both weight grads; dWh reads
+        h_{t-1} via in-kernel shifted addressing."""
+        G, BT, _ = dG_flat.shape
+        dWx, dWh, dbl = ops.grouped_wgrad_xh(
+            lc["seq_in"].reshape(G, BT, -1), lc["hs"], dG_flat, T
+        )
+        self.store.gviews[f"Wx{li}"].copy_(dWx)
+        self.store.gviews[f"Wh{li}"].copy_(dWh)
+        self.store.gviews[f"bl{li}"].copy_(dbl)
+
+    def train_batch(self, Xw, Tb) -> torch.Tensor:
+        Xw, Tb = self._pad_io(Xw, Tb)
+        G, B, T, _ = Xw.shape
+        modes = self._scan_modes(B)
+        y, cache = self._forward_seq(Xw, keep=True, modes=modes)
+        loss, dY, self.last_correct = self._loss_bwd(y, Tb)
+        dh_last = self._head_bwd(cache[-1], dY)
+
+        # BPTT through the LSTM stack
+        dSeq: Optional[torch.Tensor] = None  # grad on layer output sequence
         for li in range(len(self.lstm_meta) - 1, -1, -1):
             fin, H, rs = self.lstm_meta[li]
             lc = cache[li]
             Wh = self.store.cviews[f"Wh{li}"]
             Wx = self.store.cviews[f"Wx{li}"]
             last_only = dSeq is None
-            if li > 0 and v5_on and ops.lstm_v4_available(H, fin):
-                # v5: the dSeq GEMM rides inside the reverse scan
-                dG_flat, next_dSeq = ops.lstm_seq_bwd_fused(
-                    dh_last if last_only else dSeq,
-                    lc["gacts"], lc["cs"], Wh, Wx, last_only,
+            d_in = dh_last if last_only else dSeq
+            next_dSeq = None
+            if modes[li] == "per_step":
+                dG = self._layer_bwd_steps(li, lc, d_in, last_only)
+            elif li > 0 and modes[li] == "fused":
+                # the dSeq GEMM rides inside the reverse scan
+                dG, next_dSeq = ops.lstm_seq_bwd_fused(
+                    d_in, lc["gacts"], lc["cs"], Wh, Wx, last_only,
                     act=self.lstm_acts[li],
                 )
-                dG_flat = dG_flat.view(G, B * T, 4 * H)
             else:
-                next_dSeq = None
-                dG_flat = ops.lstm_seq_bwd(
-                    dh_last if last_only else dSeq,
-                    lc["gacts"], lc["cs"], Wh, last_only,
+                dG = ops.lstm_seq_bwd(
+                    d_in, lc["gacts"], lc["cs"], Wh, last_only,
                     act=self.lstm_acts[li],
-                ).view(G, B * T, 4 * H)
-            hs = lc["hs"]
-            # combined pass: dZ (dG) staged once for both weight grads;
-            # dWh reads h_{t-1} via in-kernel shifted addressing
-            dWx, dWh, dbl = ops.grouped_wgrad_xh(
-                lc["seq_in"].reshape(G, B * T, fin), hs, dG_flat, T
-            )
-            self.store.gviews[f"Wx{li}"].copy_(dWx)
-            self.store.gviews[f"Wh{li}"].copy_(dWh)
-            self.store.gviews[f"bl{li}"].copy_(dbl)
+                )
+            dG_flat = dG.view(G, B * T, 4 * H)
+            self._store_layer_grads(li, lc, dG_flat, T)
             # free this layer's BPTT cache before descending: the
             # allocator reuses it for the next layer's dSeq/transients
             # (whole-batch caches are the memory ceiling at G~100+).
             cache[li] = None
-            del lc, hs
-            prev_dSeq = dSeq
+            del lc, dG, d_in
             if li > 0:
                 dSeq = (
                     next_dSeq
@@ -1442,70 +1430,7 @@ class LSTMPack(BasePack):
                         G, B, T, fin
                     )
                 )
-            del dG_flat, prev_dSeq
-
-        self.store.optimizer_step()
-        return loss
-
-    def train_batch(self, Xw, Tb) -> torch.Tensor:
-        Xw, Tb = self._pad_io(Xw, Tb)
-        if self._use_fused(Xw.shape[1]):
-            return self._train_batch_fused(Xw, Tb)
-        G, B, T, _ = Xw.shape
-        y, cache = self._forward_seq(Xw, keep=True)
-        loss, dY, self.last_correct = self._loss_bwd(y, Tb)
-
-        # output dense layer backward
-        fin, fout, act = self.dense_meta
-        head = cache[-1]
-        dZ = ops.act_l1_bwd(dY, head["y"], act, 0.0)
-        dWd, dbd = ops.grouped_linear_wgrad(head["h_last"], dZ)
-        self.store.gviews["Wd"].copy_(dWd)
-        self.store.gviews["bd"].copy_(dbd)
-        dh_last = ops.grouped_linear_bwd_data(dZ, self.store.cviews["Wd"])
-
-        # BPTT through the LSTM stack
-        dSeq: Optional[torch.Tensor] = None  # grad on layer output sequence
-        for li in range(len(self.lstm_meta) - 1, -1, -1):
-            fin, H, rs = self.lstm_meta[li]
-            lc = cache[li]
-            hs, cs, gacts = lc["hs"], lc["cs"], lc["gacts"]
-            Wh = self.store.cviews[f"Wh{li}"]
-            Wx = self.store.cviews[f"Wx{li}"]
-            dG = torch.empty(
-                G, B, T, 4 * H, dtype=self.compute_dtype, device=self.device
-            )
-            dh_carry = torch.zeros(
-                G, B, H, dtype=self.compute_dtype, device=self.device
-            )
-            dc_carry = torch.zeros(G, B, H, dtype=torch.float32, device=self.device)
-            for t in range(T - 1, -1, -1):
-                dh_t = dh_carry
-                if dSeq is not None:
-                    dh_t = dh_t + dSeq[:, :, t]
-                elif li == len(self.lstm_meta) - 1 and t == T - 1:
-                    dh_t = dh_t + dh_last
-                c_prev = (
-                    cs[:, :, t - 1]
-                    if t > 0
-                    else torch.zeros_like(dc_carry)
-                )
-                dgates, dc_carry = ops.lstm_pointwise_bwd(
-                    dh_t, dc_carry, gacts[:, :, t], cs[:, :, t], c_prev,
-                    self.lstm_acts[li],
-                )
-                dG[:, :, t] = dgates
-                dh_carry = ops.grouped_linear_bwd_data(dgates, Wh)
-            # batched weight grads over all (B, T) rows
-            dG_flat = dG.view(G, B * T, 4 * H)
-            dWx, dWh, dbl = ops.grouped_wgrad_xh(
-                lc["seq_in"].reshape(G, B * T, fin), hs, dG_flat, T
-            )
-            self.store.gviews[f"Wx{li}"].copy_(dWx)
-            self.store.gviews[f"Wh{li}"].copy_(dWh)
-            self.store.gviews[f"bl{li}"].copy_(dbl)
-            if li > 0:
-                dSeq = ops.grouped_linear_bwd_data(dG_flat, Wx).view(G, B, T, fin)
+            del dG_flat
 
         self.store.optimizer_step()
         return loss

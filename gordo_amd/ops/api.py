@@ -345,56 +345,81 @@ def optimizer_step(kind, p, g, s0, s1, s2, hyper, step, p_lp=None,
     )
 
 
-def lstm_seq_fwd(xW, Wh):
-    """Fused on-device LSTM sequence scan (GPU only; H<=64 LDS-resident
-    kernels, 64<H<=256 streamed-Wh kernels).
+# ---- LSTM sequence scans: which kernel serves a call, at which row
+# tile, is decided by the extension's host-only planner
+# (csrc/scan_plan.h), which also reads the GORDO_LSTM_* switches
 
-    The software-pipelined v3 kernel (double-buffered x-gate register
-    prefetch) is the DEFAULT for the barriered H<=64 layout since the
-    round-2 GPU A/B (fwd 1.11 vs 1.51 ms, bwd 0.89 vs 0.99 ms at the
-    bench shape G=8 B=512 T=144 H=42 — gpurun validate_r2). Set
-    ``GORDO_LSTM_V1=1`` to fall back to the unpipelined v1 scan.
-    H%16==0 still takes the barrier-free v2 path inside the extension;
-    H>64 routes to the big-H kernels in both entry points."""
-    import os as _os
+def _record(family, rows, hf, has_dx, last_only) -> dict:
+    return {
+        "family": family,
+        "rows": rows,
+        "hf": hf if hf > 0 else None,
+        "has_dx": None if has_dx < 0 else bool(has_dx),
+        "last_only": None if last_only < 0 else bool(last_only),
+    }
 
-    ext = _require_hip()
-    G, B = xW.shape[0], xW.shape[1]
-    H = xW.shape[-1] // 4
-    # v2 (barrier-free, 64-row per-wave blocks) only when its grid
-    # fills the chip: at fleet G its G*ceil(B/64) blocks underfill 256
-    # CUs and the row-tiled pipelined v3 wins (call-10 rocprof: v2 bwd
-    # at 60 WGs averaged 3x the v4 fwd per launch)
-    v2_fills = H % 16 == 0 and G * ((B + 63) // 64) >= 256
-    if (
-        _os.environ.get("GORDO_LSTM_V1") == "1"
-        or H > 64            # big-H dispatch lives in the v1 entry
-        or v2_fills
-    ):
-        return ext.lstm_seq_fwd(xW, Wh)
-    return ext.lstm_seq_fwd_v3(xW, Wh)
+
+def _plan(entry, G, B, T, H, F, last_only, act):
+    *record, act, lds, blocks, err = _require_hip().scan_plan(
+        entry, G, B, T, H, F, bool(last_only), act_code(act))
+    if err:
+        return None, err
+    return dict(_record(*record), act=act, lds_bytes=lds, blocks=blocks), None
+
+
+def scan_plan(entry, G, B, T, H, F=0, last_only=False, act="tanh"):
+    """What a scan call would launch, without touching the GPU: the
+    fields of ``last_scan_launch`` plus ``act``, ``lds_bytes`` and
+    ``blocks``; ``None`` where the planner refuses (``scan_refusal``
+    has the reason). ``entry``: fwd, fwd_v1, fwd_v3, fwd_fused, bwd,
+    bwd_v1, bwd_bottom, bwd_fused, as the wrappers below name them."""
+    return _plan(entry, G, B, T, H, F, last_only, act)[0]
+
+
+def scan_refusal(entry, G, B, T, H, F=0, last_only=False, act="tanh"):
+    """The planner's message where ``scan_plan`` is None, else None."""
+    return _plan(entry, G, B, T, H, F, last_only, act)[1]
+
+
+def lstm_layer_mode(G: int, B: int, H: int, F: int, act="tanh") -> str:
+    """How the engine runs one LSTM layer: "fused" (x-GEMM inside the
+    forward scan, dX inside the backward one), "two_step" (x-GEMM,
+    then the xW scans) or "per_step" (always, without the extension)."""
+    if not hip_available():
+        return "per_step"
+    return _hip.scan_layer_mode(G, B, H, F, act_code(act))
+
+
+def lstm_seq_available(H: int) -> bool:
+    """Fused sequence-scan coverage: the LDS-resident kernels serve
+    H <= 64; the big-H kernels (Wh streamed from L2, 64-column tile
+    loop) serve 64 < H <= 256 when H % 8 == 0 — which covers the
+    reference's default LSTM dims (256, 128, 64), reference
+    gordo/machine/model/factories/lstm_autoencoder.py:112."""
+    return hip_available() and scan_plan("fwd", 1, 1, 1, H) is not None
 
 
 def lstm_v4_available(H: int, F: int) -> bool:
     """v4 fused-xW scan geometry: H <= 64, H%8==0, F%8==0, F<=128
     (the pad8 engine layout satisfies the alignment)."""
-    return hip_available() and H <= 64 and H % 8 == 0 and F % 8 == 0 \
-        and F <= 128
+    return hip_available() and \
+        scan_plan("fwd_fused", 1, 1, 1, H, F) is not None
 
 
 def lstm_act_scan_available(H: int, F: int) -> bool:
-    """Whether the fused scans serve a non-tanh cell activation at
-    this geometry. Only the v4 forward and the pipelined backward
-    kernel take one, so both must apply: the v4 geometry with F >= 8
-    and neither ``GORDO_LSTM_V4=0`` nor ``GORDO_LSTM_PIPE=0`` set."""
-    import os as _os
+    """Whether the engine's fused scans serve a non-tanh cell
+    activation at this geometry. Only the v4 forward and the pipelined
+    backward kernel take one, so both must apply."""
+    return lstm_layer_mode(1, 1, H, F, "relu") == "fused"
 
-    return (
-        lstm_v4_available(H, F)
-        and F >= 8
-        and _os.environ.get("GORDO_LSTM_V4", "1") != "0"
-        and _os.environ.get("GORDO_LSTM_PIPE", "1") != "0"
-    )
+
+def lstm_seq_fwd(xW, Wh):
+    """Fused on-device LSTM sequence scan (GPU only), by the planner's
+    public route: the pipelined v3 kernel for the barriered H <= 64
+    layout, the barrier-free v2 kernel for H % 16 == 0 once its grid
+    fills the chip, the big-H kernels for 64 < H <= 256;
+    ``GORDO_LSTM_V1=1`` takes the unpipelined v1 / v2 entry."""
+    return _require_hip().lstm_seq_fwd(xW, Wh, "fwd")
 
 
 def lstm_seq_fwd_fused(xseq, Wx, Wh, bias, store_aux=True, act="tanh"):
@@ -433,26 +458,29 @@ def lstm_seq_fwd_fused(xseq, Wx, Wh, bias, store_aux=True, act="tanh"):
 
 def lstm_seq_fwd_v3(xW, Wh):
     """The pipelined forward scan, directly (for A/B tests)."""
-    return _require_hip().lstm_seq_fwd_v3(xW, Wh)
+    return _require_hip().lstm_seq_fwd(xW, Wh, "fwd_v3")
+
+
+def _need_v2(name, H):
+    if H % 16 != 0 or H > 64:
+        raise ValueError(f"{name} needs H % 16 == 0 and H <= 64")
 
 
 def lstm_seq_fwd_v2(xW, Wh):
     """The barrier-free v2 forward scan, directly (H % 16 == 0,
-    H <= 64): the extension entry takes v2 at any grid size, without
-    the fill gate of ``lstm_seq_fwd``."""
-    H = xW.shape[-1] // 4
-    if H % 16 != 0 or H > 64:
-        raise ValueError("lstm_seq_fwd_v2 needs H % 16 == 0 and H <= 64")
-    return _require_hip().lstm_seq_fwd(xW, Wh)
+    H <= 64): the v1 entry takes v2 at any grid size, without the fill
+    gate of ``lstm_seq_fwd``."""
+    _need_v2("lstm_seq_fwd_v2", xW.shape[-1] // 4)
+    return _require_hip().lstm_seq_fwd(xW, Wh, "fwd_v1")
 
 
 def lstm_seq_bwd_v2(dSeq, gacts, cs, Wh, last_only):
     """The barrier-free v2 backward scan, directly (same geometry and
     purpose as ``lstm_seq_fwd_v2``)."""
-    H = gacts.shape[-1] // 4
-    if H % 16 != 0 or H > 64:
-        raise ValueError("lstm_seq_bwd_v2 needs H % 16 == 0 and H <= 64")
-    return _require_hip().lstm_seq_bwd(dSeq, gacts, cs, Wh, bool(last_only))
+    _need_v2("lstm_seq_bwd_v2", gacts.shape[-1] // 4)
+    return _require_hip().lstm_seq_bwd(
+        dSeq, gacts, cs, Wh, bool(last_only), "bwd_v1"
+    )
 
 
 def last_scan_launch() -> dict:
@@ -461,14 +489,7 @@ def last_scan_launch() -> dict:
     big), ``rows`` (row tile; 64 for v2), ``hf`` (H/16, v2 only, else
     None) and, for bwd_pipe only, ``has_dx`` / ``last_only`` (else
     None). Host-side record; ``family`` is "" before any launch."""
-    family, rows, hf, has_dx, last_only = _require_hip().last_scan_launch()
-    return {
-        "family": family,
-        "rows": rows,
-        "hf": hf if hf > 0 else None,
-        "has_dx": None if has_dx < 0 else bool(has_dx),
-        "last_only": None if last_only < 0 else bool(last_only),
-    }
+    return _record(*_require_hip().last_scan_launch())
 
 
 def last_scan_activation() -> str:
@@ -478,28 +499,14 @@ def last_scan_activation() -> str:
 
 
 def lstm_seq_bwd(dSeq, gacts, cs, Wh, last_only, act="tanh"):
-    """Fused on-device LSTM backward (BPTT) scan (GPU only). Same
-    version dispatch as ``lstm_seq_fwd``: pipelined v3 by default for
-    the barriered layout, v2 for H%16==0, big-H kernels for H>64;
-    ``GORDO_LSTM_V1=1`` forces the unpipelined v1 scan. A non-tanh
-    ``act`` goes straight to the ``lstm_seq_bwd_v3`` entry: only the
-    pipelined kernel behind it takes a cell activation."""
-    import os as _os
-
-    ext = _require_hip()
-    act = act_code(act)
-    if act != ACT_TANH:
-        return ext.lstm_seq_bwd_v3(dSeq, gacts, cs, Wh, bool(last_only), act)
-    G, B = gacts.shape[0], gacts.shape[1]
-    H = gacts.shape[-1] // 4
-    v2_fills = H % 16 == 0 and G * ((B + 63) // 64) >= 256
-    if (
-        _os.environ.get("GORDO_LSTM_V1") == "1"
-        or H > 64
-        or v2_fills
-    ):
-        return ext.lstm_seq_bwd(dSeq, gacts, cs, Wh, last_only)
-    return ext.lstm_seq_bwd_v3(dSeq, gacts, cs, Wh, last_only)
+    """Fused on-device LSTM backward (BPTT) scan (GPU only), by the
+    planner's public route: the same version dispatch as
+    ``lstm_seq_fwd``, with the bottom-layer entry of ``lstm_seq_bwd_v3``
+    in the place of v3. A non-tanh ``act`` goes straight to that entry:
+    only the pipelined kernel behind it takes a cell activation."""
+    return _require_hip().lstm_seq_bwd(
+        dSeq, gacts, cs, Wh, bool(last_only), "bwd", act_code(act)
+    )
 
 
 def _lstm_seq_bwd_cpu(dSeq, gacts, cs, Wh, last_only, act):
@@ -527,12 +534,13 @@ def _lstm_seq_bwd_cpu(dSeq, gacts, cs, Wh, last_only, act):
 
 
 def lstm_seq_bwd_fused(dSeq, gacts, cs, Wh, Wx, last_only, act="tanh"):
-    """v5 reverse scan with the bwd-data GEMM fused in: returns
-    (dG, dX) where dX = dG @ Wx^T computed per step against an
-    LDS-resident WxT (no dG HBM re-read). Geometry: H<=64, F<=128.
-    H%8==0 and F%8==0 take the 16-byte pipelined kernel (bit-identical
-    outputs); ``GORDO_LSTM_PIPE=0`` forces the v5 kernel. A non-tanh
-    ``act`` runs only on the pipelined kernel and raises elsewhere."""
+    """Reverse scan with the bwd-data GEMM fused in: returns (dG, dX)
+    where dX = dG @ Wx^T computed per step against an LDS-resident WxT
+    (no dG HBM re-read). Geometry: H<=64, F<=128. The planner takes the
+    16-byte pipelined kernel where it applies, else the v5 kernel
+    (bit-identical outputs); ``GORDO_LSTM_PIPE=0`` forces v5. A
+    non-tanh ``act`` runs only on the pipelined kernel and raises
+    elsewhere."""
     act = act_code(act)
     if _on_gpu(gacts):
         out = _require_hip().lstm_seq_bwd_fused(
@@ -549,14 +557,14 @@ def lstm_seq_bwd_fused(dSeq, gacts, cs, Wh, Wx, last_only, act="tanh"):
 
 def lstm_seq_bwd_v3(dSeq, gacts, cs, Wh, last_only, act="tanh"):
     """The bottom-layer backward scan, directly (for A/B tests): the
-    16-byte pipelined kernel when H % 8 == 0, else the v3 kernel;
-    ``GORDO_LSTM_PIPE=0`` forces v3. A non-tanh ``act`` runs only on
-    the pipelined kernel and raises elsewhere."""
+    16-byte pipelined kernel where the planner finds it applies, else
+    the v3 kernel; ``GORDO_LSTM_PIPE=0`` forces v3. A non-tanh ``act``
+    runs only on the pipelined kernel and raises elsewhere."""
     act = act_code(act)
     if not _on_gpu(gacts):
         return _lstm_seq_bwd_cpu(dSeq, gacts, cs, Wh, last_only, act)
-    return _require_hip().lstm_seq_bwd_v3(
-        dSeq, gacts, cs, Wh, bool(last_only), act
+    return _require_hip().lstm_seq_bwd(
+        dSeq, gacts, cs, Wh, bool(last_only), "bwd_bottom", act
     )
 
 
@@ -565,28 +573,17 @@ def lstm_seq_bwd_fused_out(dSeq, gacts, cs, Wh, Wx, last_only, dG, dX,
     """``lstm_seq_bwd_fused`` (GPU only) writing into caller-provided
     contiguous, 16-byte-aligned bf16 ``dG`` [G,B,T,4H] and ``dX``
     [G,B,T,F] — lets tests place the outputs between guard regions."""
-    _require_hip().lstm_seq_bwd_fused_out(
-        dSeq, gacts, cs, Wh, Wx, bool(last_only), dG, dX, act_code(act)
+    _require_hip().lstm_seq_bwd_fused(
+        dSeq, gacts, cs, Wh, Wx, bool(last_only), act_code(act), dG, dX
     )
 
 
 def lstm_seq_bwd_v3_out(dSeq, gacts, cs, Wh, last_only, dG, act="tanh"):
     """``lstm_seq_bwd_v3`` (GPU only, H <= 64) into a caller-provided
     ``dG`` (same contract as ``lstm_seq_bwd_fused_out``)."""
-    _require_hip().lstm_seq_bwd_v3_out(
-        dSeq, gacts, cs, Wh, bool(last_only), dG, act_code(act)
+    _require_hip().lstm_seq_bwd(
+        dSeq, gacts, cs, Wh, bool(last_only), "bwd_bottom", act_code(act), dG
     )
-
-
-def lstm_seq_available(H: int) -> bool:
-    """Fused sequence-scan coverage: the LDS-resident kernels serve
-    H <= 64; the big-H kernels (Wh streamed from L2, 64-column tile
-    loop) serve 64 < H <= 256 when H % 8 == 0 — which covers the
-    reference's default LSTM dims (256, 128, 64), reference
-    gordo/machine/model/factories/lstm_autoencoder.py:112."""
-    if not hip_available():
-        return False
-    return H <= 64 or (H <= 256 and H % 8 == 0)
 
 
 def anomaly_score(out, y, scale, minv, feat_thr, agg_thr):

@@ -968,29 +968,26 @@ std::vector<torch::Tensor> anomaly_score(
 
 // fused LSTM sequence-scan entry points (lstm_seq.hip)
 namespace gordo_lstm {
-std::vector<torch::Tensor> lstm_seq_fwd(torch::Tensor xW, torch::Tensor Wh);
+std::vector<torch::Tensor> lstm_seq_fwd(torch::Tensor xW, torch::Tensor Wh,
+                                        const std::string& entry);
 std::vector<torch::Tensor> lstm_seq_fwd_fused(torch::Tensor xseq,
                                               torch::Tensor Wx,
                                               torch::Tensor Wh,
                                               torch::Tensor bias,
                                               bool store_aux, int64_t act);
-std::vector<torch::Tensor> lstm_seq_fwd_v3(torch::Tensor xW, torch::Tensor Wh);
-torch::Tensor lstm_seq_bwd_v3(torch::Tensor dSeq, torch::Tensor gacts,
-                              torch::Tensor cs, torch::Tensor Wh,
-                              bool last_only, int64_t act);
-std::vector<torch::Tensor> lstm_seq_bwd_fused(
-    torch::Tensor dSeq, torch::Tensor gacts, torch::Tensor cs,
-    torch::Tensor Wh, torch::Tensor Wx, bool last_only, int64_t act);
 torch::Tensor lstm_seq_bwd(torch::Tensor dSeq, torch::Tensor gacts,
                            torch::Tensor cs, torch::Tensor Wh,
-                           bool last_only);
-void lstm_seq_bwd_fused_out(torch::Tensor dSeq, torch::Tensor gacts,
-                            torch::Tensor cs, torch::Tensor Wh,
-                            torch::Tensor Wx, bool last_only,
-                            torch::Tensor dG, torch::Tensor dX, int64_t act);
-void lstm_seq_bwd_v3_out(torch::Tensor dSeq, torch::Tensor gacts,
-                         torch::Tensor cs, torch::Tensor Wh, bool last_only,
-                         torch::Tensor dG, int64_t act);
+                           bool last_only, const std::string& entry,
+                           int64_t act, c10::optional<torch::Tensor> dG);
+std::vector<torch::Tensor> lstm_seq_bwd_fused(
+    torch::Tensor dSeq, torch::Tensor gacts, torch::Tensor cs,
+    torch::Tensor Wh, torch::Tensor Wx, bool last_only, int64_t act,
+    c10::optional<torch::Tensor> dG, c10::optional<torch::Tensor> dX);
+std::tuple<std::string, int, int, int, int, std::string, int64_t, int,
+           std::string>
+scan_plan(const std::string& entry, int G, int B, int T, int H, int F,
+          bool last_only, int act);
+std::string scan_layer_mode(int G, int B, int H, int F, int act);
 std::tuple<std::string, int, int, int, int> last_scan_launch();
 std::string last_scan_activation();
 }  // namespace gordo_lstm
@@ -1098,42 +1095,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "smooth call");
   mod.def("anomaly_score", &gordo_anomaly::anomaly_score,
           "fused DiffBased anomaly scoring (serving hot path)");
-  // trailing `act`: the LSTM cell activation code, tanh by default
-  mod.def("lstm_seq_bwd_v3", &gordo_lstm::lstm_seq_bwd_v3, py::arg("dSeq"),
-          py::arg("gacts"), py::arg("cs"), py::arg("Wh"),
-          py::arg("last_only"), py::arg("act") = (int64_t)ACT_TANH,
-          "pipelined fused LSTM backward scan (GORDO_LSTM_V3 opt-in)");
-  mod.def("lstm_seq_fwd_v3", &gordo_lstm::lstm_seq_fwd_v3,
-          "pipelined fused LSTM forward scan (GORDO_LSTM_V3 opt-in)");
-  mod.def("lstm_seq_fwd", &gordo_lstm::lstm_seq_fwd,
-          "fused LSTM forward sequence scan (Wh resident in LDS)");
+  // LSTM scans: `entry` names the planner's entry (scan_plan.h), `act`
+  // is the cell activation code, dG / dX optional caller-provided outputs
+  mod.def("lstm_seq_fwd", &gordo_lstm::lstm_seq_fwd, py::arg("xW"),
+          py::arg("Wh"), py::arg("entry"),
+          "fused LSTM forward sequence scan over a precomputed xW");
   mod.def("lstm_seq_fwd_fused", &gordo_lstm::lstm_seq_fwd_fused,
           py::arg("xseq"), py::arg("Wx"), py::arg("Wh"), py::arg("bias"),
           py::arg("store_aux"), py::arg("act") = (int64_t)ACT_TANH,
           "v4 scan with the x-side gate GEMM fused in (halves fwd "
           "HBM traffic); store_aux=false skips cs/gacts (inference)");
-  mod.def("lstm_seq_bwd", &gordo_lstm::lstm_seq_bwd,
+  mod.def("lstm_seq_bwd", &gordo_lstm::lstm_seq_bwd, py::arg("dSeq"),
+          py::arg("gacts"), py::arg("cs"), py::arg("Wh"),
+          py::arg("last_only"), py::arg("entry"),
+          py::arg("act") = (int64_t)ACT_TANH, py::arg("dG") = py::none(),
           "fused LSTM backward (BPTT) sequence scan");
   mod.def("lstm_seq_bwd_fused", &gordo_lstm::lstm_seq_bwd_fused,
           py::arg("dSeq"), py::arg("gacts"), py::arg("cs"), py::arg("Wh"),
           py::arg("Wx"), py::arg("last_only"),
-          py::arg("act") = (int64_t)ACT_TANH,
-          "v5 reverse scan with dSeq = dG@Wx^T fused in");
-  mod.def("lstm_seq_bwd_fused_out", &gordo_lstm::lstm_seq_bwd_fused_out,
-          py::arg("dSeq"), py::arg("gacts"), py::arg("cs"), py::arg("Wh"),
-          py::arg("Wx"), py::arg("last_only"), py::arg("dG"), py::arg("dX"),
-          py::arg("act") = (int64_t)ACT_TANH,
-          "lstm_seq_bwd_fused into caller-provided dG, dX");
+          py::arg("act") = (int64_t)ACT_TANH, py::arg("dG") = py::none(),
+          py::arg("dX") = py::none(),
+          "reverse scan with dX = dG@Wx^T fused in");
+  mod.def("scan_plan", &gordo_lstm::scan_plan,
+          "(family, rows, hf, has_dx, last_only, act, lds_bytes, blocks, "
+          "error) the planner gives a scan request; host only");
+  mod.def("scan_layer_mode", &gordo_lstm::scan_layer_mode,
+          "fused / two_step / per_step for one LSTM layer; host only");
   mod.def("last_scan_activation", &gordo_lstm::last_scan_activation,
           "cell activation name of this thread's last scan-kernel launch");
   mod.def("last_scan_launch", &gordo_lstm::last_scan_launch,
           "(family, rows, hf, has_dx, last_only) of this thread's last "
           "scan-kernel launch");
-  mod.def("lstm_seq_bwd_v3_out", &gordo_lstm::lstm_seq_bwd_v3_out,
-          py::arg("dSeq"), py::arg("gacts"), py::arg("cs"), py::arg("Wh"),
-          py::arg("last_only"), py::arg("dG"),
-          py::arg("act") = (int64_t)ACT_TANH,
-          "lstm_seq_bwd_v3 into a caller-provided dG");
   mod.def("grouped_linear_fwd", &grouped_linear_fwd,
           "Y = act(X@W + b) per group (MFMA)");
   mod.def("grouped_linear_bwd_data", &grouped_linear_bwd_data,

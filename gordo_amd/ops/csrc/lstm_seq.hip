@@ -1826,406 +1826,98 @@ __global__ __launch_bounds__(256) void lstm_seq_fwd_v4_kernel(
 
 // ---------------------------------------------------------------------------
 namespace gordo_lstm {
+}  // reopened below the planner's header
+
+// Host side. scan_plan.h decides what is launched (family, row tile,
+// LDS bytes, grid); the entries below prepare tensors, take the plan,
+// and launch it through one mechanism that also writes the launch
+// record, so the record cannot disagree with what ran.
+#include "scan_plan.h"
+
+namespace gordo_lstm {
+
+static_assert(ACT_LINEAR == CELL_LINEAR && ACT_TANH == CELL_TANH &&
+                  ACT_RELU == CELL_RELU && ACT_SIGMOID == CELL_SIGMOID &&
+                  PLAN_LDK == LDK,
+              "scan_plan.h must agree with the kernels' constants");
 
 // Launch record: which scan kernel the calling thread launched last
-// (host-only; tests assert the dispatch arm they mean to exercise).
-// rows is the row tile (64 for v2, whose HF = H/16 goes in hf);
-// has_dx / last_only are -1 outside the pipelined backward.
-struct ScanLaunch {
-  const char* family = "";
-  int rows = 0;
-  int hf = 0;
-  int has_dx = -1;
-  int last_only = -1;
-};
-thread_local ScanLaunch g_last_launch;
-// cell activation of that launch, kept beside the record (whose five
-// fields are compared whole); "tanh" for every tanh-only family
-thread_local const char* g_last_act = "tanh";
+// (host-only; tests assert the dispatch arm they mean to exercise):
+// the plan's family, rows, hf, has_dx, last_only and act.
+thread_local ScanPlan g_last_launch = refuse("nothing launched yet");
 
-inline const char* act_name(int act) {
-  switch (act) {
-    case CELL_LINEAR: return "linear";
-    case CELL_RELU: return "relu";
-    case CELL_SIGMOID: return "sigmoid";
-    default: return "tanh";
-  }
-}
-
-inline void check_act(int64_t act) {
-  TORCH_CHECK(act >= CELL_LINEAR && act <= CELL_SIGMOID,
-              "unknown LSTM cell activation code ", act);
-}
-
-inline void note_launch(const char* family, int rows, int hf = 0,
-                        int has_dx = -1, int last_only = -1,
-                        int act = CELL_TANH) {
-  g_last_launch = ScanLaunch{family, rows, hf, has_dx, last_only};
-  g_last_act = act_name(act);
-}
-
-std::string last_scan_activation() { return std::string(g_last_act); }
+std::string last_scan_activation() { return act_name(g_last_launch.act); }
 
 std::tuple<std::string, int, int, int, int> last_scan_launch() {
-  const ScanLaunch& l = g_last_launch;
-  return {std::string(l.family), l.rows, l.hf, l.has_dx, l.last_only};
+  const ScanPlan& l = g_last_launch;
+  return {l.ok() ? l.family_name() : "", l.rows, l.hf, l.has_dx,
+          l.last_only};
 }
 
-// pad 4H up to the MFMA K-step (32) plus 8: the K loop's last
-// fragment read may touch columns [H4, ru32(H4)); they must exist in
-// the row and be zero.
-inline int pad_ldg(int h4) { return ((h4 + 31) & ~31) + 8; }
-
-inline int pick_rows(int G, int B) {
-  // smallest row tile whose grid reaches ~2 workgroups per CU: the
-  // scans are latency-bound chains, so co-resident workgroups on one
-  // CU overlap each other's stalls (WhT is staged once per launch, so
-  // smaller tiles do not re-read Wh). GORDO_LSTM_ROWS forces a tile
-  // for A/B measurement.
-  if (const char* e = getenv("GORDO_LSTM_ROWS")) {
-    int r = atoi(e);
-    if (r == 16 || r == 32 || r == 64) return r;
-  }
-  if (G * ((B + 63) / 64) >= 512) return 64;
-  if (G * ((B + 31) / 32) >= 512) return 32;
-  return 16;
+ScanEntry entry_of(const std::string& name) {
+  for (int e = 0; e < N_ENTRIES; ++e)
+    if (name == ENTRY_NAMES[e]) return (ScanEntry)e;
+  TORCH_CHECK(false, "unknown scan entry '", name, "'");
 }
 
-// ---- big-H path (64 < H <= 256, H % 8 == 0) ----
-inline bool big_ok(int H) { return H > 64 && H <= 256 && H % 8 == 0; }
-
-inline size_t big_lds(int rows, int H, int ldg, int Kp) {
-  int LDH = Kp + 8;
-  return (size_t)rows * LDH * 2 + (size_t)rows * ldg * 2 +
-         (size_t)rows * H * 4;
+// (family, rows, hf, has_dx, last_only, act, lds_bytes, blocks, error):
+// the plan of a request, without touching the GPU
+std::tuple<std::string, int, int, int, int, std::string, int64_t, int,
+           std::string>
+scan_plan(const std::string& entry, int G, int B, int T, int H, int F,
+          bool last_only, int act) {
+  ScanPlan p = plan_scan({entry_of(entry), G, B, T, H, F, last_only, act},
+                         ScanEnv::read());
+  return {p.ok() ? p.family_name() : "", p.rows, p.hf, p.has_dx, p.last_only,
+          act_name(p.act), (int64_t)p.lds_bytes, p.blocks, p.error};
 }
 
-inline int pick_rows_big(int B, int H, int ldg, int Kp) {
-  // 64-row tiles halve the per-step Wh L2 re-reads (each workgroup
-  // streams the whole Wh every timestep) — use them whenever the LDS
-  // fits AND the batch actually fills the tile.
-  if (B >= 48 && big_lds(64, H, ldg, Kp) <= 160 * 1024) return 64;
-  return 32;
+std::string scan_layer_mode(int G, int B, int H, int F, int act) {
+  return layer_mode(ScanEnv::read(), G, B, H, F, act);
 }
 
-std::vector<torch::Tensor> lstm_seq_fwd_big(torch::Tensor xW,
-                                            torch::Tensor Wh) {
-  TORCH_CHECK(xW.is_cuda() && xW.dim() == 4, "xW must be [G,B,T,4H] on GPU");
-  auto xc = xW.to(torch::kBFloat16).contiguous();
-  auto Whc = Wh.to(torch::kBFloat16).contiguous();
-  int G = xc.size(0), B = xc.size(1), T = xc.size(2), H4 = xc.size(3);
-  int H = H4 / 4;
-  TORCH_CHECK(big_ok(H), "lstm_seq_fwd_big needs 64 < H <= 256, H % 8 == 0");
-  int Kp = (H + 31) & ~31;
-  int ldg = pad_ldg(H4);
-  // pre-transpose Wh -> [G, 4H, Kp] (zero-padded K) once per launch so
-  // B-fragment loads are 16-byte k-contiguous
-  auto WhT = torch::zeros({G, H4, Kp},
-                          Whc.options().dtype(torch::kBFloat16));
-  WhT.narrow(2, 0, H).copy_(Whc.transpose(1, 2));
-  WhT = WhT.contiguous();
-  auto hs = torch::empty({G, B, T, H}, xc.options());
-  auto cs = torch::empty({G, B, T, H}, xc.options().dtype(torch::kFloat32));
-  auto gacts = torch::empty({G, B, T, H4}, xc.options());
-  int rows = pick_rows_big(B, H, ldg, Kp);
-  size_t lds = big_lds(rows, H, ldg, Kp);
-  TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded (big fwd)");
-  int blocks = G * ((B + rows - 1) / rows);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  note_launch("fwd_big", rows);
-  if (rows == 64)
-    hipLaunchKernelGGL(lstm_seq_fwd_big_kernel<64>, dim3(blocks), dim3(256),
-                       lds, stream, (const bf16*)xc.data_ptr(),
-                       (const bf16*)WhT.data_ptr(), (bf16*)hs.data_ptr(),
-                       cs.data_ptr<float>(), (bf16*)gacts.data_ptr(), B, T, H,
-                       ldg, Kp);
-  else
-    hipLaunchKernelGGL(lstm_seq_fwd_big_kernel<32>, dim3(blocks), dim3(256),
-                       lds, stream, (const bf16*)xc.data_ptr(),
-                       (const bf16*)WhT.data_ptr(), (bf16*)hs.data_ptr(),
-                       cs.data_ptr<float>(), (bf16*)gacts.data_ptr(), B, T, H,
-                       ldg, Kp);
-  return {hs, cs, gacts};
+inline ScanPlan planned(const ScanRequest& q) {
+  ScanPlan p = plan_scan(q, ScanEnv::read());
+  TORCH_CHECK(p.ok(), p.error);
+  return p;
 }
 
-torch::Tensor lstm_seq_bwd_big(torch::Tensor dSeq, torch::Tensor gacts,
-                               torch::Tensor cs, torch::Tensor Wh,
-                               bool last_only) {
-  TORCH_CHECK(gacts.is_cuda() && gacts.dim() == 4, "gacts must be [G,B,T,4H]");
-  auto dc = dSeq.to(torch::kBFloat16).contiguous();
-  auto gc = gacts.to(torch::kBFloat16).contiguous();
-  auto ccs = cs.to(torch::kFloat32).contiguous();
-  auto Whc = Wh.to(torch::kBFloat16).contiguous();
-  int G = gc.size(0), B = gc.size(1), T = gc.size(2), H4 = gc.size(3);
-  int H = H4 / 4;
-  TORCH_CHECK(big_ok(H), "lstm_seq_bwd_big needs 64 < H <= 256, H % 8 == 0");
-  int Kp = (H + 31) & ~31;
-  int ldg = pad_ldg(H4);
-  auto dG = torch::empty_like(gc);
-  int rows = pick_rows_big(B, H, ldg, Kp);
-  size_t lds = big_lds(rows, H, ldg, Kp);
-  TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded (big bwd)");
-  int blocks = G * ((B + rows - 1) / rows);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  note_launch("bwd_big", rows);
-  if (rows == 64)
-    hipLaunchKernelGGL(lstm_seq_bwd_big_kernel<64>, dim3(blocks), dim3(256),
-                       lds, stream, (const bf16*)dc.data_ptr(),
-                       (const bf16*)gc.data_ptr(), ccs.data_ptr<float>(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)dG.data_ptr(), B,
-                       T, H, ldg, last_only ? 1 : 0);
-  else
-    hipLaunchKernelGGL(lstm_seq_bwd_big_kernel<32>, dim3(blocks), dim3(256),
-                       lds, stream, (const bf16*)dc.data_ptr(),
-                       (const bf16*)gc.data_ptr(), ccs.data_ptr<float>(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)dG.data_ptr(), B,
-                       T, H, ldg, last_only ? 1 : 0);
-  return dG;
+// Maps a runtime value onto a template argument: f is called with the
+// std::integral_constant of the V that equals v.
+template <int... Vs, class Fn>
+inline void pick(int v, Fn&& f) {
+  const bool hit =
+      ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+  TORCH_CHECK(hit, "no scan kernel instantiated for ", v);
+}
+template <class Fn>
+inline void pick(bool v, Fn&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <class Fn>
+inline void pick_tile(int rows, Fn&& f) {
+  pick<16, 32, 64>(rows, f);
+}
+template <class Fn>
+inline void pick_act(int act, Fn&& f) {
+  pick<CELL_LINEAR, CELL_TANH, CELL_RELU, CELL_SIGMOID>(act, f);
 }
 
-inline bool v4_ok(int H, int F) {
-  return H <= 64 && H % 8 == 0 && F % 8 == 0 && F <= 128;
+template <class Kernel, class... Args>
+inline void launch(Kernel kernel, const ScanPlan& p, Args... args) {
+  g_last_launch = p;
+  hipLaunchKernelGGL(kernel, dim3(p.blocks), dim3(256), p.lds_bytes,
+                     at::cuda::getCurrentCUDAStream().stream(), args...);
 }
 
-std::vector<torch::Tensor> lstm_seq_fwd_fused(torch::Tensor xseq,
-                                              torch::Tensor Wx,
-                                              torch::Tensor Wh,
-                                              torch::Tensor bias,
-                                              bool store_aux, int64_t act) {
-  // xseq [G,B,T,F]; Wx [G,F,4H]; Wh [G,H,4H]; bias [G,4H].
-  // Computes the x-side gate GEMM inside the scan (see kernel note).
-  // This is the only forward scan with a cell activation parameter,
-  // and an unsupported geometry raises for every act.
-  TORCH_CHECK(xseq.is_cuda() && xseq.dim() == 4,
-              "xseq must be [G,B,T,F] on GPU");
-  check_act(act);
-  auto xc = xseq.to(torch::kBFloat16).contiguous();
-  auto Wxc = Wx.to(torch::kBFloat16);
-  auto Whc = Wh.to(torch::kBFloat16);
-  auto bc = bias.to(torch::kBFloat16).contiguous();
-  int G = xc.size(0), B = xc.size(1), T = xc.size(2), F = xc.size(3);
-  int H = Whc.size(1), H4 = 4 * H;
-  TORCH_CHECK(v4_ok(H, F), "lstm_seq_fwd_fused geometry unsupported");
-  int Kc = H + F;
-  int LDKc = ((Kc + 31) & ~31) + 8;
-  int ldg = pad_ldg(H4);
-  // concatenated transposed weights [G, 4H, Kc] = [Wh ; Wx]^T
-  auto Wcat = torch::cat({Whc, Wxc}, 1).transpose(1, 2).contiguous();
-  auto hs = torch::empty({G, B, T, H}, xc.options());
-  auto cs = store_aux
-                ? torch::empty({G, B, T, H},
-                               xc.options().dtype(torch::kFloat32))
-                : torch::empty({1}, xc.options().dtype(torch::kFloat32));
-  auto gacts = store_aux ? torch::empty({G, B, T, H4}, xc.options())
-                         : torch::empty({1}, xc.options());
-  int rows = pick_rows(G, B);
-  // the pre-activation tile is fp32 for a non-tanh act (gate_tile_t)
-  const size_t gate_bytes = act == CELL_TANH ? 2 : 4;
-  auto lds_for = [&](int r) {
-    return (size_t)H4 * LDKc * 2 + (size_t)r * LDKc * 2 +
-           (size_t)r * ldg * gate_bytes + (size_t)ldg * 2 +
-           (size_t)r * H * 4;
-  };
-  while (rows > 16 && lds_for(rows) > 160 * 1024) rows /= 2;
-  size_t lds = lds_for(rows);
-  TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded (v4 fwd)");
-  int blocks = G * ((B + rows - 1) / rows);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  auto xp = (const bf16*)xc.data_ptr();
-  auto wp = (const bf16*)Wcat.data_ptr();
-  auto bp = (const bf16*)bc.data_ptr();
-  auto hp = (bf16*)hs.data_ptr();
-  auto cp = cs.data_ptr<float>();
-  auto gp = (bf16*)gacts.data_ptr();
-  #define V4_LAUNCH(R, S, A)                                            \
-    hipLaunchKernelGGL((lstm_seq_fwd_v4_kernel<R, S, A>), dim3(blocks), \
-                       dim3(256), lds, stream, xp, wp, bp, hp, cp, gp,  \
-                       B, T, H, F, ldg)
-  #define V4_ROWS(S, A)                                                 \
-    do {                                                                \
-      if (rows == 64) V4_LAUNCH(64, S, A);                              \
-      else if (rows == 32) V4_LAUNCH(32, S, A);                         \
-      else V4_LAUNCH(16, S, A);                                         \
-    } while (0)
-  #define V4_AUX(A)                                                     \
-    do {                                                                \
-      if (store_aux) V4_ROWS(true, A);                                  \
-      else V4_ROWS(false, A);                                           \
-    } while (0)
-  note_launch("fwd_v4", rows, 0, -1, -1, (int)act);
-  switch ((int)act) {
-    case CELL_LINEAR: V4_AUX(CELL_LINEAR); break;
-    case CELL_RELU: V4_AUX(CELL_RELU); break;
-    case CELL_SIGMOID: V4_AUX(CELL_SIGMOID); break;
-    default: V4_AUX(CELL_TANH); break;
-  }
-  #undef V4_AUX
-  #undef V4_ROWS
-  #undef V4_LAUNCH
-  if (store_aux) return {hs, cs, gacts};
-  return {hs};
+inline torch::Tensor as_bf16(const torch::Tensor& t) {
+  return t.to(torch::kBFloat16).contiguous();
 }
-
-std::vector<torch::Tensor> lstm_seq_fwd(torch::Tensor xW, torch::Tensor Wh) {
-  TORCH_CHECK(xW.is_cuda() && xW.dim() == 4, "xW must be [G,B,T,4H] on GPU");
-  if (xW.size(3) / 4 > 64) return lstm_seq_fwd_big(xW, Wh);
-  auto xc = xW.to(torch::kBFloat16).contiguous();
-  auto Whc = Wh.to(torch::kBFloat16).contiguous();
-  int G = xc.size(0), B = xc.size(1), T = xc.size(2), H4 = xc.size(3);
-  int H = H4 / 4;
-  TORCH_CHECK(H <= 64, "lstm_seq_fwd supports H <= 64");
-  int ldg = pad_ldg(H4);
-  auto hs = torch::empty({G, B, T, H}, xc.options());
-  auto cs = torch::empty({G, B, T, H}, xc.options().dtype(torch::kFloat32));
-  auto gacts = torch::empty({G, B, T, H4}, xc.options());
-  int rows = pick_rows(G, B);
-  size_t lds = (size_t)H4 * LDK * 2 + (size_t)rows * LDK * 2 +
-               (size_t)rows * ldg * 2 + (size_t)rows * H * 4;
-  TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded");
-  int blocks = G * ((B + rows - 1) / rows);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  if (H % 16 == 0) {
-    // v2: register-resident gate math, no barriers in the T loop
-    int blocks2 = G * ((B + 63) / 64);
-    size_t lds2 = (size_t)H4 * LDK * 2 + (size_t)4 * 16 * LDK * 2;
-    auto xp = (const bf16*)xc.data_ptr();
-    auto wp = (const bf16*)Whc.data_ptr();
-    auto hp = (bf16*)hs.data_ptr();
-    auto cp = cs.data_ptr<float>();
-    auto gp = (bf16*)gacts.data_ptr();
-    note_launch("fwd_v2", 64, H / 16);
-    switch (H / 16) {
-      case 1: hipLaunchKernelGGL(lstm_seq_fwd_v2_kernel<1>, dim3(blocks2),
-                                 dim3(256), lds2, stream, xp, wp, hp, cp, gp,
-                                 B, T); break;
-      case 2: hipLaunchKernelGGL(lstm_seq_fwd_v2_kernel<2>, dim3(blocks2),
-                                 dim3(256), lds2, stream, xp, wp, hp, cp, gp,
-                                 B, T); break;
-      case 3: hipLaunchKernelGGL(lstm_seq_fwd_v2_kernel<3>, dim3(blocks2),
-                                 dim3(256), lds2, stream, xp, wp, hp, cp, gp,
-                                 B, T); break;
-      default: hipLaunchKernelGGL(lstm_seq_fwd_v2_kernel<4>, dim3(blocks2),
-                                 dim3(256), lds2, stream, xp, wp, hp, cp, gp,
-                                 B, T); break;
-    }
-    return {hs, cs, gacts};
-  }
-  note_launch("fwd_v1", rows);
-  if (rows == 64)
-    hipLaunchKernelGGL(lstm_seq_fwd_kernel<64>, dim3(blocks), dim3(256), lds,
-                       stream, (const bf16*)xc.data_ptr(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)hs.data_ptr(),
-                       cs.data_ptr<float>(), (bf16*)gacts.data_ptr(), B, T, H,
-                       ldg);
-  else if (rows == 32)
-    hipLaunchKernelGGL(lstm_seq_fwd_kernel<32>, dim3(blocks), dim3(256), lds,
-                       stream, (const bf16*)xc.data_ptr(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)hs.data_ptr(),
-                       cs.data_ptr<float>(), (bf16*)gacts.data_ptr(), B, T, H,
-                       ldg);
-  else
-    hipLaunchKernelGGL(lstm_seq_fwd_kernel<16>, dim3(blocks), dim3(256), lds,
-                       stream, (const bf16*)xc.data_ptr(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)hs.data_ptr(),
-                       cs.data_ptr<float>(), (bf16*)gacts.data_ptr(), B, T, H,
-                       ldg);
-  return {hs, cs, gacts};
+inline const bf16* rd(const torch::Tensor& t) {
+  return (const bf16*)t.data_ptr();
 }
-
-std::vector<torch::Tensor> lstm_seq_fwd_v3(torch::Tensor xW,
-                                            torch::Tensor Wh) {
-  // identical contract to lstm_seq_fwd, pipelined kernel (always the
-  // barriered layout, never the v2 path: v3 is measured against v1 on
-  // the same shapes). H > 64 routes to the big-H kernel (no v3 there).
-  TORCH_CHECK(xW.is_cuda() && xW.dim() == 4, "xW must be [G,B,T,4H] on GPU");
-  if (xW.size(3) / 4 > 64) return lstm_seq_fwd_big(xW, Wh);
-  auto xc = xW.to(torch::kBFloat16).contiguous();
-  auto Whc = Wh.to(torch::kBFloat16).contiguous();
-  int G = xc.size(0), B = xc.size(1), T = xc.size(2), H4 = xc.size(3);
-  int H = H4 / 4;
-  TORCH_CHECK(H <= 64, "lstm_seq_fwd_v3 supports H <= 64");
-  int ldg = pad_ldg(H4);
-  auto hs = torch::empty({G, B, T, H}, xc.options());
-  auto cs = torch::empty({G, B, T, H}, xc.options().dtype(torch::kFloat32));
-  auto gacts = torch::empty({G, B, T, H4}, xc.options());
-  int rows = pick_rows(G, B);
-  size_t lds = (size_t)H4 * LDK * 2 + (size_t)rows * LDK * 2 +
-               (size_t)rows * ldg * 2 + (size_t)rows * H * 4;
-  TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded");
-  int blocks = G * ((B + rows - 1) / rows);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  note_launch("fwd_v3", rows);
-  if (rows == 64)
-    hipLaunchKernelGGL(lstm_seq_fwd_v3_kernel<64>, dim3(blocks), dim3(256),
-                       lds, stream, (const bf16*)xc.data_ptr(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)hs.data_ptr(),
-                       cs.data_ptr<float>(), (bf16*)gacts.data_ptr(), B, T, H,
-                       ldg);
-  else if (rows == 32)
-    hipLaunchKernelGGL(lstm_seq_fwd_v3_kernel<32>, dim3(blocks), dim3(256),
-                       lds, stream, (const bf16*)xc.data_ptr(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)hs.data_ptr(),
-                       cs.data_ptr<float>(), (bf16*)gacts.data_ptr(), B, T, H,
-                       ldg);
-  else
-    hipLaunchKernelGGL(lstm_seq_fwd_v3_kernel<16>, dim3(blocks), dim3(256),
-                       lds, stream, (const bf16*)xc.data_ptr(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)hs.data_ptr(),
-                       cs.data_ptr<float>(), (bf16*)gacts.data_ptr(), B, T, H,
-                       ldg);
-  return {hs, cs, gacts};
-}
-
-
-// ---- pipelined backward scan dispatch ----
-// GORDO_LSTM_PIPE=0 (read per call) restores the v5 / v3 kernels.
-inline bool pipe_enabled() {
-  const char* e = getenv("GORDO_LSTM_PIPE");
-  return !(e && e[0] == '0' && e[1] == '\0');
-}
-
-// F = 0 for the bottom-layer scan (no Wx tile, no dX staging)
-inline size_t pipe_lds(int r, int H, int F, int ldg, bool last_only) {
-  size_t ring_row = (size_t)(H / 8) * (last_only ? 6 : 7) * 16;
-  return (size_t)(H + F) * ldg * 2 + (size_t)r * ldg * 2 +
-         (size_t)r * LDK * 2 + (size_t)r * H * 4 + 2 * (size_t)r * ring_row +
-         (size_t)r * F * 2;
-}
-
-// row tile for the pipelined kernel, 0 when it does not apply: the
-// geometry (16-byte rows), 32-bit per-block store offsets, and the
-// 160 KB LDS budget after halving the tile down to 16 rows
-inline int pipe_rows(int rows, int T, int H, int F, bool has_dx, int ldg,
-                     bool last_only) {
-  if (!pipe_enabled()) return 0;
-  if (H < 8 || H > 64 || H % 8 != 0 || T < 1) return 0;
-  if (has_dx && (F < 8 || F > 128 || F % 8 != 0)) return 0;
-  if ((size_t)64 * T * 256 >= ((size_t)1 << 31)) return 0;
-  while (rows > 16 && pipe_lds(rows, H, F, ldg, last_only) > 160 * 1024)
-    rows /= 2;
-  return pipe_lds(rows, H, F, ldg, last_only) <= 160 * 1024 ? rows : 0;
-}
-
-#define GORDO_PIPE_LAUNCH(R, DX, LO, A)                                    \
-  hipLaunchKernelGGL((lstm_seq_bwd_pipe_kernel<R, DX, LO, A>),             \
-                     dim3(blocks), dim3(256), lds, stream, dp, gp, cp,     \
-                     whp, wxp, dgp, dxp, B, T, H, F, ldg)
-#define GORDO_PIPE_ROWS_A(DX, LO, A)                                       \
-  do {                                                                     \
-    if (rows == 64) GORDO_PIPE_LAUNCH(64, DX, LO, A);                      \
-    else if (rows == 32) GORDO_PIPE_LAUNCH(32, DX, LO, A);                 \
-    else GORDO_PIPE_LAUNCH(16, DX, LO, A);                                 \
-  } while (0)
-// the cell activation `act` (an int in scope) picks the instantiation
-#define GORDO_PIPE_ROWS(DX, LO)                                            \
-  do {                                                                     \
-    switch (act) {                                                         \
-      case CELL_LINEAR: GORDO_PIPE_ROWS_A(DX, LO, CELL_LINEAR); break;     \
-      case CELL_RELU: GORDO_PIPE_ROWS_A(DX, LO, CELL_RELU); break;         \
-      case CELL_SIGMOID: GORDO_PIPE_ROWS_A(DX, LO, CELL_SIGMOID); break;   \
-      default: GORDO_PIPE_ROWS_A(DX, LO, CELL_TANH); break;                \
-    }                                                                      \
-  } while (0)
+inline bf16* wr(const torch::Tensor& t) { return (bf16*)t.data_ptr(); }
 
 inline void check_out(const torch::Tensor& out, const torch::Tensor& like,
                       std::vector<int64_t> shape, const char* what) {
@@ -2236,257 +1928,214 @@ inline void check_out(const torch::Tensor& out, const torch::Tensor& like,
               what, " must be a contiguous 16-byte-aligned bf16 tensor of "
               "the output shape on the inputs' device");
 }
+// a caller-provided output (tests place them inside guard regions), or
+// a fresh one
+inline torch::Tensor out_or_new(const c10::optional<torch::Tensor>& out,
+                                const torch::Tensor& like,
+                                std::vector<int64_t> shape, const char* what) {
+  if (!out) return torch::empty(shape, like.options());
+  check_out(*out, like, shape, what);
+  return *out;
+}
 
-std::vector<torch::Tensor> lstm_seq_bwd_fused_impl(
+// Forward scan over a precomputed xW [G,B,T,4H] with Wh [G,H,4H], by
+// the entries "fwd" (public route), "fwd_v1" and "fwd_v3": returns
+// {hs, cs, gacts}.
+std::vector<torch::Tensor> lstm_seq_fwd(torch::Tensor xW, torch::Tensor Wh,
+                                        const std::string& entry) {
+  TORCH_CHECK(xW.is_cuda() && xW.dim() == 4, "xW must be [G,B,T,4H] on GPU");
+  const ScanEntry e = entry_of(entry);
+  TORCH_CHECK(e == FWD || e == FWD_V1 || e == FWD_V3,
+              "lstm_seq_fwd takes the xW entries, not '", entry, "'");
+  auto xc = as_bf16(xW);
+  auto Whc = as_bf16(Wh);
+  int G = xc.size(0), B = xc.size(1), T = xc.size(2), H4 = xc.size(3);
+  int H = H4 / 4;
+  const ScanPlan p = planned({e, G, B, T, H, 0, false, CELL_TANH});
+  auto hs = torch::empty({G, B, T, H}, xc.options());
+  auto cs = torch::empty({G, B, T, H}, xc.options().dtype(torch::kFloat32));
+  auto gacts = torch::empty({G, B, T, H4}, xc.options());
+  float* cp = cs.data_ptr<float>();
+  switch (p.family) {
+    case FWD_BIG: {
+      // pre-transpose Wh -> [G, 4H, Kp] (zero-padded K) once per launch
+      // so B-fragment loads are 16-byte k-contiguous
+      int Kp = round32(H);
+      auto WhT = torch::zeros({G, H4, Kp}, Whc.options());
+      WhT.narrow(2, 0, H).copy_(Whc.transpose(1, 2));
+      pick<32, 64>(p.rows, [&](auto R) {
+        launch(lstm_seq_fwd_big_kernel<decltype(R)::value>, p, rd(xc),
+               rd(WhT), wr(hs), cp, wr(gacts), B, T, H, p.ldg, Kp);
+      });
+      break;
+    }
+    case FWD_K2:
+      pick<1, 2, 3, 4>(p.hf, [&](auto HF) {
+        launch(lstm_seq_fwd_v2_kernel<decltype(HF)::value>, p, rd(xc),
+               rd(Whc), wr(hs), cp, wr(gacts), B, T);
+      });
+      break;
+    case FWD_K1:
+      pick_tile(p.rows, [&](auto R) {
+        launch(lstm_seq_fwd_kernel<decltype(R)::value>, p, rd(xc), rd(Whc),
+               wr(hs), cp, wr(gacts), B, T, H, p.ldg);
+      });
+      break;
+    default:  // FWD_K3
+      pick_tile(p.rows, [&](auto R) {
+        launch(lstm_seq_fwd_v3_kernel<decltype(R)::value>, p, rd(xc),
+               rd(Whc), wr(hs), cp, wr(gacts), B, T, H, p.ldg);
+      });
+  }
+  return {hs, cs, gacts};
+}
+
+// v4 forward: xseq [G,B,T,F]; Wx [G,F,4H]; Wh [G,H,4H]; bias [G,4H].
+// Computes the x-side gate GEMM inside the scan (see kernel note).
+// This is the only forward scan with a cell activation parameter, and
+// an unsupported geometry raises for every act.
+std::vector<torch::Tensor> lstm_seq_fwd_fused(torch::Tensor xseq,
+                                              torch::Tensor Wx,
+                                              torch::Tensor Wh,
+                                              torch::Tensor bias,
+                                              bool store_aux, int64_t act) {
+  TORCH_CHECK(xseq.is_cuda() && xseq.dim() == 4,
+              "xseq must be [G,B,T,F] on GPU");
+  auto xc = as_bf16(xseq);
+  auto Wxc = Wx.to(torch::kBFloat16);
+  auto Whc = Wh.to(torch::kBFloat16);
+  auto bc = as_bf16(bias);
+  int G = xc.size(0), B = xc.size(1), T = xc.size(2), F = xc.size(3);
+  int H = Whc.size(1), H4 = 4 * H;
+  const ScanPlan p = planned({FWD_FUSED, G, B, T, H, F, false, (int)act});
+  // concatenated transposed weights [G, 4H, H + F] = [Wh ; Wx]^T
+  auto Wcat = torch::cat({Whc, Wxc}, 1).transpose(1, 2).contiguous();
+  auto f32 = xc.options().dtype(torch::kFloat32);
+  auto hs = torch::empty({G, B, T, H}, xc.options());
+  auto cs = store_aux ? torch::empty({G, B, T, H}, f32)
+                      : torch::empty({1}, f32);
+  auto gacts = store_aux ? torch::empty({G, B, T, H4}, xc.options())
+                         : torch::empty({1}, xc.options());
+  pick_tile(p.rows, [&](auto R) {
+    pick(store_aux, [&](auto AUX) {
+      pick_act(p.act, [&](auto A) {
+        launch(lstm_seq_fwd_v4_kernel<decltype(R)::value,
+                                      decltype(AUX)::value,
+                                      decltype(A)::value>,
+               p, rd(xc), rd(Wcat), rd(bc), wr(hs), cs.data_ptr<float>(),
+               wr(gacts), B, T, H, F, p.ldg);
+      });
+    });
+  });
+  if (store_aux) return {hs, cs, gacts};
+  return {hs};
+}
+
+// the pipelined backward, with Wx / dX (fused) or without (F = 0)
+inline void launch_pipe(const ScanPlan& p, const bf16* d, const bf16* g,
+                        const float* c, const bf16* wh, const bf16* wx,
+                        bf16* dg, bf16* dx, int B, int T, int H, int F) {
+  pick_tile(p.rows, [&](auto R) {
+    pick(p.has_dx == 1, [&](auto DX) {
+      pick(p.last_only == 1, [&](auto LO) {
+        pick_act(p.act, [&](auto A) {
+          launch(lstm_seq_bwd_pipe_kernel<decltype(R)::value,
+                                          decltype(DX)::value,
+                                          decltype(LO)::value,
+                                          decltype(A)::value>,
+                 p, d, g, c, wh, wx, dg, dx, B, T, H, F, p.ldg);
+        });
+      });
+    });
+  });
+}
+
+// Reverse scan with dX_t = dG_t @ Wx^T fused in: returns {dG, dX},
+// written into dG_out / dX_out where given. The pipelined kernel, else
+// (tanh only) v5. Geometry: H <= 64, F <= 128.
+std::vector<torch::Tensor> lstm_seq_bwd_fused(
     torch::Tensor dSeq, torch::Tensor gacts, torch::Tensor cs,
-    torch::Tensor Wh, torch::Tensor Wx, bool last_only,
-    c10::optional<torch::Tensor> dG_out, c10::optional<torch::Tensor> dX_out,
-    int64_t act64) {
-  // returns {dG, dX}: the reverse scan with dSeq_t = dG_t @ Wx^T
-  // fused in (see kernel note). Geometry: H <= 64, F <= 128.
+    torch::Tensor Wh, torch::Tensor Wx, bool last_only, int64_t act,
+    c10::optional<torch::Tensor> dG_out,
+    c10::optional<torch::Tensor> dX_out) {
   TORCH_CHECK(gacts.is_cuda() && gacts.dim() == 4, "gacts must be [G,B,T,4H]");
-  check_act(act64);
-  const int act = (int)act64;
-  auto dc = dSeq.to(torch::kBFloat16).contiguous();
-  auto gc = gacts.to(torch::kBFloat16).contiguous();
-  auto ccs = cs.to(torch::kFloat32).contiguous();
-  auto Whc = Wh.to(torch::kBFloat16).contiguous();
-  auto Wxc = Wx.to(torch::kBFloat16).contiguous();
+  auto dc = as_bf16(dSeq);
+  auto gc = as_bf16(gacts);
+  auto cc = cs.to(torch::kFloat32).contiguous();
+  auto Whc = as_bf16(Wh);
+  auto Wxc = as_bf16(Wx);
   int G = gc.size(0), B = gc.size(1), T = gc.size(2), H4 = gc.size(3);
   int H = H4 / 4, F = Wxc.size(1);
-  TORCH_CHECK(H <= 64 && F <= 128, "lstm_seq_bwd_fused geometry");
-  int ldg = pad_ldg(H4);
-  if (dG_out) check_out(*dG_out, gc, {G, B, T, H4}, "dG");
-  if (dX_out) check_out(*dX_out, gc, {G, B, T, F}, "dX");
-  auto dG = dG_out ? *dG_out : torch::empty_like(gc);
-  auto dX = dX_out ? *dX_out : torch::empty({G, B, T, F}, gc.options());
-  int rows = pick_rows(G, B);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  auto dp = (const bf16*)dc.data_ptr();
-  auto gp = (const bf16*)gc.data_ptr();
-  auto cp = ccs.data_ptr<float>();
-  auto whp = (const bf16*)Whc.data_ptr();
-  auto wxp = (const bf16*)Wxc.data_ptr();
-  auto dgp = (bf16*)dG.data_ptr();
-  auto dxp = (bf16*)dX.data_ptr();
-  if (int prow = pipe_rows(rows, T, H, F, true, ldg, last_only)) {
-    rows = prow;
-    size_t lds = pipe_lds(rows, H, F, ldg, last_only);
-    int blocks = G * ((B + rows - 1) / rows);
-    note_launch("bwd_pipe", rows, 0, 1, last_only ? 1 : 0, act);
-    if (last_only) GORDO_PIPE_ROWS(true, true);
-    else GORDO_PIPE_ROWS(true, false);
-    return {dG, dX};
-  }
-  // only the pipelined kernel takes a cell activation
-  TORCH_CHECK(act == CELL_TANH, "lstm_seq_bwd_fused: cell activation '",
-              act_name(act), "' needs the pipelined kernel (H % 8 == 0, "
-              "8 <= H <= 64, F % 8 == 0, 8 <= F <= 128, T < 2^17, "
-              "GORDO_LSTM_PIPE != 0)");
-  auto lds_for = [&](int r) {
-    return (size_t)H * ldg * 2 + (size_t)F * ldg * 2 +
-           (size_t)r * ldg * 2 + (size_t)r * LDK * 2 + (size_t)r * H * 4;
-  };
-  while (rows > 16 && lds_for(rows) > 160 * 1024) rows /= 2;
-  size_t lds = lds_for(rows);
-  TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded (v5 bwd)");
-  int blocks = G * ((B + rows - 1) / rows);
-  int lo = last_only ? 1 : 0;
-  note_launch("bwd_v5", rows);
-  if (rows == 64)
-    hipLaunchKernelGGL(lstm_seq_bwd_v5_kernel<64>, dim3(blocks), dim3(256),
-                       lds, stream, dp, gp, cp, whp, wxp, dgp, dxp, B, T,
-                       H, F, ldg, lo);
-  else if (rows == 32)
-    hipLaunchKernelGGL(lstm_seq_bwd_v5_kernel<32>, dim3(blocks), dim3(256),
-                       lds, stream, dp, gp, cp, whp, wxp, dgp, dxp, B, T,
-                       H, F, ldg, lo);
+  const ScanPlan p = planned({BWD_FUSED, G, B, T, H, F, last_only, (int)act});
+  auto dG = out_or_new(dG_out, gc, {G, B, T, H4}, "dG");
+  auto dX = out_or_new(dX_out, gc, {G, B, T, F}, "dX");
+  if (p.family == BWD_PIPE)
+    launch_pipe(p, rd(dc), rd(gc), cc.data_ptr<float>(), rd(Whc), rd(Wxc),
+                wr(dG), wr(dX), B, T, H, F);
   else
-    hipLaunchKernelGGL(lstm_seq_bwd_v5_kernel<16>, dim3(blocks), dim3(256),
-                       lds, stream, dp, gp, cp, whp, wxp, dgp, dxp, B, T,
-                       H, F, ldg, lo);
+    pick_tile(p.rows, [&](auto R) {
+      launch(lstm_seq_bwd_v5_kernel<decltype(R)::value>, p, rd(dc), rd(gc),
+             cc.data_ptr<float>(), rd(Whc), rd(Wxc), wr(dG), wr(dX), B, T, H,
+             F, p.ldg, last_only ? 1 : 0);
+    });
   return {dG, dX};
 }
 
-std::vector<torch::Tensor> lstm_seq_bwd_fused(
-    torch::Tensor dSeq, torch::Tensor gacts, torch::Tensor cs,
-    torch::Tensor Wh, torch::Tensor Wx, bool last_only, int64_t act) {
-  return lstm_seq_bwd_fused_impl(dSeq, gacts, cs, Wh, Wx, last_only,
-                                 c10::nullopt, c10::nullopt, act);
-}
-
-// the same scan writing into caller-provided dG / dX (tests place them
-// inside guard regions)
-void lstm_seq_bwd_fused_out(torch::Tensor dSeq, torch::Tensor gacts,
-                            torch::Tensor cs, torch::Tensor Wh,
-                            torch::Tensor Wx, bool last_only,
-                            torch::Tensor dG, torch::Tensor dX,
-                            int64_t act) {
-  lstm_seq_bwd_fused_impl(dSeq, gacts, cs, Wh, Wx, last_only, dG, dX, act);
-}
-
-torch::Tensor lstm_seq_bwd_v3_impl(torch::Tensor dSeq, torch::Tensor gacts,
-                                   torch::Tensor cs, torch::Tensor Wh,
-                                   bool last_only,
-                                   c10::optional<torch::Tensor> dG_out,
-                                   int64_t act64) {
-  // identical contract to lstm_seq_bwd; pipelined kernel, always the
-  // barriered layout (A/B-tested against v1 on the same shapes).
-  // H > 64 routes to the big-H kernel (no v3 there).
-  TORCH_CHECK(gacts.is_cuda() && gacts.dim() == 4, "gacts must be [G,B,T,4H]");
-  check_act(act64);
-  const int act = (int)act64;
-  const char* need_pipe =
-      "' needs the pipelined kernel (H % 8 == 0, 8 <= H <= 64, T < 2^17, "
-      "GORDO_LSTM_PIPE != 0)";
-  if (gacts.size(3) / 4 > 64) {
-    TORCH_CHECK(act == CELL_TANH, "lstm_seq_bwd_v3: cell activation '",
-                act_name(act), need_pipe);
-    TORCH_CHECK(!dG_out, "no out variant on the big-H path");
-    return lstm_seq_bwd_big(dSeq, gacts, cs, Wh, last_only);
-  }
-  auto dc = dSeq.to(torch::kBFloat16).contiguous();
-  auto gc = gacts.to(torch::kBFloat16).contiguous();
-  auto cc = cs.to(torch::kFloat32).contiguous();
-  auto Whc = Wh.to(torch::kBFloat16).contiguous();
-  int G = gc.size(0), B = gc.size(1), T = gc.size(2), H4 = gc.size(3);
-  int H = H4 / 4;
-  TORCH_CHECK(H <= 64, "lstm_seq_bwd_v3 supports H <= 64");
-  int ldg = pad_ldg(H4);
-  if (dG_out) check_out(*dG_out, gc, {G, B, T, H4}, "dG");
-  auto dG = dG_out ? *dG_out : torch::empty_like(gc);
-  int rows = pick_rows(G, B);
-  if (int prow = pipe_rows(rows, T, H, 0, false, ldg, last_only)) {
-    rows = prow;
-    const int F = 0;
-    size_t lds = pipe_lds(rows, H, F, ldg, last_only);
-    int blocks = G * ((B + rows - 1) / rows);
-    auto stream = at::cuda::getCurrentCUDAStream().stream();
-    auto dp = (const bf16*)dc.data_ptr();
-    auto gp = (const bf16*)gc.data_ptr();
-    auto cp = cc.data_ptr<float>();
-    auto whp = (const bf16*)Whc.data_ptr();
-    const bf16* wxp = nullptr;
-    auto dgp = (bf16*)dG.data_ptr();
-    bf16* dxp = nullptr;
-    note_launch("bwd_pipe", rows, 0, 0, last_only ? 1 : 0, act);
-    if (last_only) GORDO_PIPE_ROWS(false, true);
-    else GORDO_PIPE_ROWS(false, false);
-    return dG;
-  }
-  TORCH_CHECK(act == CELL_TANH, "lstm_seq_bwd_v3: cell activation '",
-              act_name(act), need_pipe);
-  size_t lds = (size_t)H * ldg * 2 + (size_t)rows * ldg * 2 +
-               (size_t)rows * LDK * 2 + (size_t)rows * H * 4;
-  TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded");
-  int blocks = G * ((B + rows - 1) / rows);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  note_launch("bwd_v3", rows);
-  if (rows == 64)
-    hipLaunchKernelGGL(lstm_seq_bwd_v3_kernel<64>, dim3(blocks), dim3(256),
-                       lds, stream, (const bf16*)dc.data_ptr(),
-                       (const bf16*)gc.data_ptr(), cc.data_ptr<float>(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)dG.data_ptr(), B,
-                       T, H, ldg, last_only ? 1 : 0);
-  else if (rows == 32)
-    hipLaunchKernelGGL(lstm_seq_bwd_v3_kernel<32>, dim3(blocks), dim3(256),
-                       lds, stream, (const bf16*)dc.data_ptr(),
-                       (const bf16*)gc.data_ptr(), cc.data_ptr<float>(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)dG.data_ptr(), B,
-                       T, H, ldg, last_only ? 1 : 0);
-  else
-    hipLaunchKernelGGL(lstm_seq_bwd_v3_kernel<16>, dim3(blocks), dim3(256),
-                       lds, stream, (const bf16*)dc.data_ptr(),
-                       (const bf16*)gc.data_ptr(), cc.data_ptr<float>(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)dG.data_ptr(), B,
-                       T, H, ldg, last_only ? 1 : 0);
-  return dG;
-}
-
-torch::Tensor lstm_seq_bwd_v3(torch::Tensor dSeq, torch::Tensor gacts,
-                              torch::Tensor cs, torch::Tensor Wh,
-                              bool last_only, int64_t act) {
-  return lstm_seq_bwd_v3_impl(dSeq, gacts, cs, Wh, last_only, c10::nullopt,
-                              act);
-}
-
-void lstm_seq_bwd_v3_out(torch::Tensor dSeq, torch::Tensor gacts,
-                         torch::Tensor cs, torch::Tensor Wh, bool last_only,
-                         torch::Tensor dG, int64_t act) {
-  lstm_seq_bwd_v3_impl(dSeq, gacts, cs, Wh, last_only, dG, act);
-}
-
+// Reverse scan without Wx, by the entries "bwd" (public route),
+// "bwd_v1" and "bwd_bottom": returns dG, written into dG_out where
+// given (H <= 64 only).
 torch::Tensor lstm_seq_bwd(torch::Tensor dSeq, torch::Tensor gacts,
                            torch::Tensor cs, torch::Tensor Wh,
-                           bool last_only) {
+                           bool last_only, const std::string& entry,
+                           int64_t act,
+                           c10::optional<torch::Tensor> dG_out) {
   TORCH_CHECK(gacts.is_cuda() && gacts.dim() == 4, "gacts must be [G,B,T,4H]");
-  if (gacts.size(3) / 4 > 64)
-    return lstm_seq_bwd_big(dSeq, gacts, cs, Wh, last_only);
-  auto dc = dSeq.to(torch::kBFloat16).contiguous();
-  auto gc = gacts.to(torch::kBFloat16).contiguous();
+  const ScanEntry e = entry_of(entry);
+  TORCH_CHECK(e == BWD || e == BWD_V1 || e == BWD_BOTTOM,
+              "lstm_seq_bwd takes the entries without Wx, not '", entry, "'");
+  auto dc = as_bf16(dSeq);
+  auto gc = as_bf16(gacts);
   auto cc = cs.to(torch::kFloat32).contiguous();
-  auto Whc = Wh.to(torch::kBFloat16).contiguous();
+  auto Whc = as_bf16(Wh);
   int G = gc.size(0), B = gc.size(1), T = gc.size(2), H4 = gc.size(3);
   int H = H4 / 4;
-  TORCH_CHECK(H <= 64, "lstm_seq_bwd supports H <= 64");
-  int ldg = pad_ldg(H4);
-  auto dG = torch::empty_like(gc);
-  int rows = pick_rows(G, B);
-  size_t lds = (size_t)H * ldg * 2 + (size_t)rows * ldg * 2 +
-               (size_t)rows * LDK * 2 + (size_t)rows * H * 4;
-  TORCH_CHECK(lds <= 160 * 1024, "LDS budget exceeded");
-  int blocks = G * ((B + rows - 1) / rows);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  if (H % 16 == 0) {
-    int blocks2 = G * ((B + 63) / 64);
-    size_t lds2 = (size_t)H * ldg * 2 + (size_t)4 * 16 * ldg * 2;
-    auto dp = (const bf16*)dc.data_ptr();
-    auto gp = (const bf16*)gc.data_ptr();
-    auto cp = cc.data_ptr<float>();
-    auto wp = (const bf16*)Whc.data_ptr();
-    auto op = (bf16*)dG.data_ptr();
-    int lo = last_only ? 1 : 0;
-    note_launch("bwd_v2", 64, H / 16);
-    switch (H / 16) {
-      case 1: hipLaunchKernelGGL(lstm_seq_bwd_v2_kernel<1>, dim3(blocks2),
-                                 dim3(256), lds2, stream, dp, gp, cp, wp, op,
-                                 B, T, ldg, lo); break;
-      case 2: hipLaunchKernelGGL(lstm_seq_bwd_v2_kernel<2>, dim3(blocks2),
-                                 dim3(256), lds2, stream, dp, gp, cp, wp, op,
-                                 B, T, ldg, lo); break;
-      case 3: hipLaunchKernelGGL(lstm_seq_bwd_v2_kernel<3>, dim3(blocks2),
-                                 dim3(256), lds2, stream, dp, gp, cp, wp, op,
-                                 B, T, ldg, lo); break;
-      default: hipLaunchKernelGGL(lstm_seq_bwd_v2_kernel<4>, dim3(blocks2),
-                                 dim3(256), lds2, stream, dp, gp, cp, wp, op,
-                                 B, T, ldg, lo); break;
-    }
-    return dG;
+  const ScanPlan p = planned({e, G, B, T, H, 0, last_only, (int)act});
+  TORCH_CHECK(!dG_out || p.family != BWD_BIG,
+              "no out variant on the big-H path");
+  auto dG = out_or_new(dG_out, gc, {G, B, T, H4}, "dG");
+  const float* cp = cc.data_ptr<float>();
+  const int lo = last_only ? 1 : 0;
+  // v1, v3 and big share one signature
+  auto tiled = [&](auto kernel) {
+    launch(kernel, p, rd(dc), rd(gc), cp, rd(Whc), wr(dG), B, T, H, p.ldg, lo);
+  };
+  switch (p.family) {
+    case BWD_PIPE:
+      launch_pipe(p, rd(dc), rd(gc), cp, rd(Whc), nullptr, wr(dG), nullptr, B,
+                  T, H, 0);
+      break;
+    case BWD_BIG:
+      pick<32, 64>(p.rows, [&](auto R) {
+        tiled(lstm_seq_bwd_big_kernel<decltype(R)::value>);
+      });
+      break;
+    case BWD_K2:
+      pick<1, 2, 3, 4>(p.hf, [&](auto HF) {
+        launch(lstm_seq_bwd_v2_kernel<decltype(HF)::value>, p, rd(dc), rd(gc),
+               cp, rd(Whc), wr(dG), B, T, p.ldg, lo);
+      });
+      break;
+    case BWD_K1:
+      pick_tile(p.rows, [&](auto R) {
+        tiled(lstm_seq_bwd_kernel<decltype(R)::value>);
+      });
+      break;
+    default:  // BWD_K3
+      pick_tile(p.rows, [&](auto R) {
+        tiled(lstm_seq_bwd_v3_kernel<decltype(R)::value>);
+      });
   }
-  note_launch("bwd_v1", rows);
-  if (rows == 64)
-    hipLaunchKernelGGL(lstm_seq_bwd_kernel<64>, dim3(blocks), dim3(256), lds,
-                       stream, (const bf16*)dc.data_ptr(),
-                       (const bf16*)gc.data_ptr(), cc.data_ptr<float>(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)dG.data_ptr(), B,
-                       T, H, ldg, last_only ? 1 : 0);
-  else if (rows == 32)
-    hipLaunchKernelGGL(lstm_seq_bwd_kernel<32>, dim3(blocks), dim3(256), lds,
-                       stream, (const bf16*)dc.data_ptr(),
-                       (const bf16*)gc.data_ptr(), cc.data_ptr<float>(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)dG.data_ptr(), B,
-                       T, H, ldg, last_only ? 1 : 0);
-  else
-    hipLaunchKernelGGL(lstm_seq_bwd_kernel<16>, dim3(blocks), dim3(256), lds,
-                       stream, (const bf16*)dc.data_ptr(),
-                       (const bf16*)gc.data_ptr(), cc.data_ptr<float>(),
-                       (const bf16*)Whc.data_ptr(), (bf16*)dG.data_ptr(), B,
-                       T, H, ldg, last_only ? 1 : 0);
   return dG;
 }
-
-#undef GORDO_PIPE_ROWS
-#undef GORDO_PIPE_ROWS_A
-#undef GORDO_PIPE_LAUNCH
 
 }  // namespace gordo_lstm
