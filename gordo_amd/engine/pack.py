@@ -84,7 +84,18 @@ def pad_enabled(device) -> bool:
     of g). Every supported loss is 0 with zero gradient at d=0, so pad
     output columns add nothing; only the mean needs the REAL element
     count (ops.loss_bwd real_f). CPU packs stay unpadded (they are the
-    fp32 oracle)."""
+    fp32 oracle).
+
+    GRU packs (reset_after cell) pad as well. A pad unit has zero
+    weights and bias, so z = r = σ(0) = 0.5, q = 0, n = tanh(0) = 0 and
+    h = 0.5·h_prev + 0.5·0 = 0 from h_{-1} = 0: it emits nothing. Its dh
+    is 0 at every step, because the next layer's pad ROWS are zero (no
+    dX into it) and the carry dh·z + dGh·Wh^T starts at 0 and only adds
+    products with dh (= 0) or with the pad COLUMNS of Wh (= 0). With
+    dh = 0 its da_z, da_r, da_n and dq are 0, which zeroes the grads of
+    its weight columns; the grads of its weight rows are h_prev^T·dGh
+    with h_prev = 0 (Wh) or zero pad inputs (Wx). Every gradient of a
+    pad weight is exactly 0."""
     return (
         torch.device(device).type == "cuda"
         and os.environ.get("GORDO_PAD8", "1") != "0"
@@ -1114,30 +1125,31 @@ class LSTMPack(BasePack):
     models.py:713-793)."""
 
     @staticmethod
-    def _gate_converters(H, pH, row_l):
+    def _gate_converters(H, pH, row_l, n_gates=4):
         """Logical<->physical converters for gate-interleaved LSTM
         params: physical gate blocks are pH wide (padded), logical H —
-        so slicing alone can't extract them."""
+        so slicing alone can't extract them. ``n_gates``: 4 for LSTM,
+        3 for GRU (whose [2, 3H] bias takes the 2-D branch whole)."""
         def extract(arr):
             if arr.ndim == 1:
                 return np.concatenate(
-                    [arr[gb * pH : gb * pH + H] for gb in range(4)]
+                    [arr[gb * pH : gb * pH + H] for gb in range(n_gates)]
                 ).copy()
             r = arr[:row_l] if row_l else arr
             return np.concatenate(
-                [r[:, gb * pH : gb * pH + H] for gb in range(4)], axis=1
+                [r[:, gb * pH : gb * pH + H] for gb in range(n_gates)], axis=1
             ).copy()
 
         def insert(view, t):
             view.zero_()
             if view.dim() == 1:
-                for gb in range(4):
+                for gb in range(n_gates):
                     view[gb * pH : gb * pH + H].copy_(
                         t[gb * H : (gb + 1) * H]
                     )
             else:
                 rl = row_l if row_l else view.shape[0]
-                for gb in range(4):
+                for gb in range(n_gates):
                     view[:rl, gb * pH : gb * pH + H].copy_(
                         t[:, gb * H : (gb + 1) * H]
                     )
@@ -1482,3 +1494,148 @@ class LSTMPack(BasePack):
             Xw, _ = self._gather_batch(X, dummyY, idx)
             outs.append(self.predict_windows(Xw))
         return torch.cat(outs, dim=1)
+
+
+class GRUPack(LSTMPack):
+    """Grouped stacked-GRU trainer: the Keras 3 ``GRU`` default cell
+    (reset_after=True, gate order z, r, n, bias [2, 3H]) over the same
+    windowed series, parameter store, early stopping, compaction and
+    serialization as ``LSTMPack``. Each layer is one ``ops.gru_seq_fwd``
+    launch forward and one ``ops.gru_seq_bwd`` launch backward; the
+    weight grads are the grouped kernels the LSTM uses. There is no
+    per-timestep GRU path: on a GPU, shapes the scan planner refuses
+    (H > 64, F > 128, or GORDO_PAD8=0 with widths that are no multiple
+    of 8) raise at construction with the planner's message."""
+
+    def _declare_params(self):
+        spec = self.spec
+        gru_layers = [l for l in spec.layers if l.kind == "gru"]
+        dense_layers = [l for l in spec.layers if l.kind == "dense"]
+        assert len(dense_layers) == 1 and len(gru_layers) + 1 == len(
+            spec.layers), "GRU spec must be [GRU..., Dense]"
+        p = self._pad
+        self.lstm_acts = ["tanh"] * len(gru_layers)
+        self.lstm_meta = []          # PHYSICAL (fin, H, return_sequences)
+        self.lstm_meta_logical = []  # logical dims for serialization
+        fin_l = self._logical_in = spec.n_features
+        for i, layer in enumerate(gru_layers):
+            H_l = layer.units
+            fin, H = p(fin_l), p(H_l)
+            if self.device.type == "cuda":
+                self._check_planned(fin, H, has_dx=i > 0)
+            regs = layer.weight_regs()
+            self.store.declare(f"Wx{i}", (self.G, fin, 3 * H),
+                               logical=(self.G, fin_l, 3 * H_l),
+                               reg=regs["kernel"])
+            self.store.declare(f"Wh{i}", (self.G, H, 3 * H),
+                               logical=(self.G, H_l, 3 * H_l),
+                               reg=regs["recurrent"])
+            self.store.declare(f"bl{i}", (self.G, 2, 3 * H),
+                               logical=(self.G, 2, 3 * H_l),
+                               reg=regs["bias"])
+            if H != H_l or fin != fin_l:
+                for name, row_l in ((f"Wx{i}", fin_l), (f"Wh{i}", H_l),
+                                    (f"bl{i}", None)):
+                    self._extractors[name] = self._gate_converters(
+                        H_l, H, row_l, n_gates=3
+                    )
+            self.lstm_meta.append((fin, H, layer.return_sequences))
+            self.lstm_meta_logical.append((fin_l, H_l, layer.return_sequences))
+            fin_l = H_l
+        out_layer = dense_layers[0]
+        self._logical_out = out_layer.units
+        self.dense_meta = (p(fin_l), p(out_layer.units), out_layer.activation)
+        self.dense_meta_logical = (fin_l, out_layer.units, out_layer.activation)
+        out_regs = out_layer.weight_regs()
+        self.store.declare("Wd", (self.G, p(fin_l), p(out_layer.units)),
+                           logical=(self.G, fin_l, out_layer.units),
+                           reg=out_regs["kernel"])
+        self.store.declare("bd", (self.G, p(out_layer.units)),
+                           logical=(self.G, out_layer.units),
+                           reg=out_regs["bias"])
+
+    def _check_planned(self, fin, H, has_dx):
+        """Raise with the scan planner's message where it refuses a
+        layer (the batch size plays no part in a refusal)."""
+        T = max(int(self.spec.lookback_window), 1)
+        for args in (("fwd", self.G, 1, T, H, fin),
+                     ("bwd", self.G, 1, T, H, fin if has_dx else 0, has_dx)):
+            why = ops.gru_refusal(*args)
+            if why:
+                raise ValueError(
+                    f"GRU layer ({fin} -> {H}) has no scan kernel: {why}"
+                )
+
+    def _init_weights(self):
+        # as Keras: glorot-uniform kernel, orthogonal recurrent blocks,
+        # zero bias; logical draws in the CPU pack's RNG order, then
+        # scattered into the padded gate blocks
+        for g in range(self.G):
+            gen = torch.Generator().manual_seed(int(self.seeds[g]) & 0x7FFFFFFF)
+            for i, (fin_l, H_l, _rs) in enumerate(self.lstm_meta_logical):
+                wx = _glorot_uniform((fin_l, 3 * H_l), gen)
+                wh = torch.cat(
+                    [_orthogonal((H_l, H_l), gen) for _ in range(3)], dim=1
+                )
+                self._insert_logical(
+                    f"Wx{i}", self.store.views[f"Wx{i}"][g], wx.numpy()
+                )
+                self._insert_logical(
+                    f"Wh{i}", self.store.views[f"Wh{i}"][g], wh.numpy()
+                )
+                self.store.views[f"bl{i}"][g].zero_()
+            fin_l, fout_l, _act = self.dense_meta_logical
+            wd = _glorot_uniform((fin_l, fout_l), gen)
+            self.store.views["Wd"][g][:fin_l, :fout_l].copy_(wd)
+
+    def _scan_modes(self, B: Optional[int] = None) -> List[str]:
+        return ["fused"] * len(self.lstm_meta)
+
+    def _layer_fwd_scan(self, li, mode, seq, keep):
+        out = ops.gru_seq_fwd(
+            seq, self.store.cviews[f"Wx{li}"], self.store.cviews[f"Wh{li}"],
+            self.store.views[f"bl{li}"], store_aux=keep,
+        )
+        return out[0], None, (out[1] if keep else None)
+
+    def train_batch(self, Xw, Tb) -> torch.Tensor:
+        Xw, Tb = self._pad_io(Xw, Tb)
+        G, B, T, _ = Xw.shape
+        y, cache = self._forward_seq(Xw, keep=True)
+        loss, dY, self.last_correct = self._loss_bwd(y, Tb)
+        d_in = self._head_bwd(cache[-1], dY)
+
+        # BPTT through the GRU stack: dX rides inside the reverse scan
+        # of every layer but the bottom one
+        last_only = True
+        for li in range(len(self.lstm_meta) - 1, -1, -1):
+            fin, H, _rs = self.lstm_meta[li]
+            lc = cache[li]
+            out = ops.gru_seq_bwd(
+                d_in, lc["gacts"], lc["hs"], self.store.cviews[f"Wh{li}"],
+                last_only,
+                Wx=self.store.cviews[f"Wx{li}"] if li > 0 else None,
+            )
+            dWx, dbx = ops.grouped_linear_wgrad(
+                lc["seq_in"].reshape(G, B * T, fin),
+                out[0].view(G, B * T, 3 * H),
+            )
+            dWh, dbh = ops.grouped_linear_wgrad_hprev(
+                lc["hs"], out[1].view(G, B * T, 3 * H), T
+            )
+            self.store.gviews[f"Wx{li}"].copy_(dWx)
+            self.store.gviews[f"Wh{li}"].copy_(dWh)
+            self.store.gviews[f"bl{li}"][:, 0].copy_(dbx)
+            self.store.gviews[f"bl{li}"][:, 1].copy_(dbh)
+            cache[li] = None  # free this layer's BPTT cache
+            d_in = out[2] if li > 0 else None
+            last_only = False
+            del lc, out
+
+        self.store.optimizer_step()
+        return loss
+
+
+def pack_class(spec: ModelSpec):
+    """The pack that trains a spec: by its model_type."""
+    return {"lstm": LSTMPack, "gru": GRUPack}.get(spec.model_type, DensePack)

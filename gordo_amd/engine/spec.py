@@ -298,14 +298,14 @@ def parse_weight_regularizer(reg_def: Any, owner: str = "regularizer"
 
 @dataclass
 class LayerSpec:
-    kind: str  # "dense" | "lstm"
+    kind: str  # "dense" | "lstm" | "gru"
     units: int
     activation: str = "tanh"
     l1_activity: float = 0.0  # L1 activity regularizer weight (dense)
     return_sequences: bool = True  # lstm only
     # weight regularizers (Keras kernel_ / bias_ / recurrent_regularizer):
     # each adds l1 sum|w| + l2 sum w^2 over its tensor to the model's
-    # loss. The recurrent pair is legal only on lstm.
+    # loss. The recurrent pair is legal only on lstm and gru.
     kernel_l1: float = 0.0
     kernel_l2: float = 0.0
     bias_l1: float = 0.0
@@ -318,7 +318,9 @@ class LayerSpec:
             setattr(self, name, _reg_coefficient(
                 f"{self.kind} layer", name, getattr(self, name)
             ))
-        if self.kind != "lstm" and (self.recurrent_l1 or self.recurrent_l2):
+        if self.kind not in ("lstm", "gru") and (
+            self.recurrent_l1 or self.recurrent_l2
+        ):
             raise ValueError(
                 f"recurrent_regularizer on a {self.kind} layer: only LSTM "
                 "layers have a recurrent kernel"
@@ -357,7 +359,7 @@ def _layer_dict(d: Dict[str, Any]) -> Dict[str, Any]:
 
 @dataclass
 class ModelSpec:
-    model_type: str  # "feedforward" | "lstm"
+    model_type: str  # "feedforward" | "lstm" | "gru"
     n_features: int
     n_features_out: int
     layers: List[LayerSpec] = field(default_factory=list)
@@ -411,6 +413,11 @@ class ModelSpec:
         d = dict(d)
         d["layers"] = [LayerSpec.from_dict(x) for x in d.get("layers", [])]
         return cls(**d)
+
+    @property
+    def recurrent(self) -> bool:
+        """A windowed stack of LSTM or GRU layers under one Dense."""
+        return self.model_type in ("lstm", "gru")
 
     # ---- shape helpers -------------------------------------------------
     def dense_dims(self) -> List[tuple]:

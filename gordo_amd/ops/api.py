@@ -586,6 +586,78 @@ def lstm_seq_bwd_v3_out(dSeq, gacts, cs, Wh, last_only, dG, act="tanh"):
     )
 
 
+# ---- GRU sequence scans (csrc/gru_seq.hip): the Keras 3 reset_after
+# cell, gate order z, r, n, bias [G, 2, 3H]. One kernel per direction,
+# planned by scan_plan.h's plan_gru(); there is no other GPU route, so a
+# shape the planner refuses raises with its message.
+
+def _gru_plan(fwd, G, B, T, H, F, has_dx, last_only):
+    family, rows, dx, lo, lds, blocks, err = _require_hip().gru_plan(
+        bool(fwd), G, B, T, H, F, bool(has_dx), bool(last_only))
+    if err:
+        return None, err
+    return _gru_record(family, rows, dx, lo, lds, blocks), None
+
+
+def _gru_record(family, rows, has_dx, last_only, lds, blocks) -> dict:
+    return {
+        "family": family,
+        "rows": rows,
+        "has_dx": None if has_dx < 0 else bool(has_dx),
+        "last_only": None if last_only < 0 else bool(last_only),
+        "lds_bytes": lds,
+        "blocks": blocks,
+    }
+
+
+def gru_plan(direction, G, B, T, H, F=0, has_dx=False, last_only=False):
+    """What a GRU scan call would launch, without touching the GPU:
+    ``family`` (gru_fwd / gru_bwd), ``rows``, ``has_dx`` / ``last_only``
+    (backward only, else None), ``lds_bytes`` and ``blocks``; ``None``
+    where the planner refuses (``gru_refusal`` has the reason).
+    ``direction`` is "fwd" or "bwd"; a backward without dX has F = 0."""
+    return _gru_plan(direction == "fwd", G, B, T, H, F, has_dx, last_only)[0]
+
+
+def gru_refusal(direction, G, B, T, H, F=0, has_dx=False, last_only=False):
+    """The planner's message where ``gru_plan`` is None, else None."""
+    return _gru_plan(direction == "fwd", G, B, T, H, F, has_dx, last_only)[1]
+
+
+def last_gru_launch() -> dict:
+    """The plan of this thread's last ``gru_seq_*`` launch (the fields
+    of ``gru_plan``); ``family`` is "" before any launch."""
+    return _gru_record(*_require_hip().last_gru_launch())
+
+
+def gru_seq_fwd(xseq, Wx, Wh, bias, store_aux=True):
+    """GRU forward scan with the x-side gate GEMM inside the recurrence:
+    xseq [G,B,T,F], Wx [G,F,3H], Wh [G,H,3H], bias [G,2,3H] ->
+    ``(hs [G,B,T,H], gacts [G,B,T,4H])`` with gacts = {z, r, n, q}, or
+    ``(hs,)`` with ``store_aux=False`` (inference; same hs bit for
+    bit). CPU tensors take the reference recurrence in their dtype."""
+    if _on_gpu(xseq):
+        return tuple(_require_hip().gru_seq_fwd(
+            xseq, Wx, Wh, bias, bool(store_aux)))
+    hs, gacts = ref.gru_seq_fwd_ref(xseq, Wx, Wh, bias, dtype=xseq.dtype,
+                                    round_points=False)
+    return (hs, gacts) if store_aux else (hs,)
+
+
+def gru_seq_bwd(dSeq, gacts, hs, Wh, last_only, Wx=None):
+    """GRU reverse scan: ``(dGx, dGh)`` [G,B,T,3H], the gate grads of
+    the kernel side and of the recurrent side (they differ in the
+    candidate block), plus ``dX = dGx @ Wx^T`` [G,B,T,F] computed inside
+    the scan when ``Wx`` is given. Weight grads follow from
+    ``grouped_linear_wgrad(seq_in, dGx)`` and
+    ``grouped_linear_wgrad_hprev(hs, dGh, T)``."""
+    if _on_gpu(gacts):
+        return tuple(_require_hip().gru_seq_bwd(
+            dSeq, gacts, hs, Wh, bool(last_only), Wx))
+    return ref.gru_seq_bwd_ref(dSeq, gacts, hs, Wh, last_only, Wx=Wx,
+                               dtype=gacts.dtype, round_points=False)
+
+
 def anomaly_score(out, y, scale, minv, feat_thr, agg_thr):
     """Fused serving-path anomaly scoring (GPU only; callers fall back
     to numpy/pandas on CPU — machine/model/anomaly/diff.py)."""

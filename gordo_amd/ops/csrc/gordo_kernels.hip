@@ -992,6 +992,21 @@ std::tuple<std::string, int, int, int, int> last_scan_launch();
 std::string last_scan_activation();
 }  // namespace gordo_lstm
 
+// fused GRU sequence-scan entry points (gru_seq.hip)
+namespace gordo_gru {
+std::vector<torch::Tensor> gru_seq_fwd(torch::Tensor xseq, torch::Tensor Wx,
+                                       torch::Tensor Wh, torch::Tensor bias,
+                                       bool store_aux);
+std::vector<torch::Tensor> gru_seq_bwd(torch::Tensor dSeq,
+                                       torch::Tensor gacts, torch::Tensor hs,
+                                       torch::Tensor Wh, bool last_only,
+                                       c10::optional<torch::Tensor> Wx);
+std::tuple<std::string, int, int, int, int64_t, int, std::string> gru_plan(
+    bool fwd, int G, int B, int T, int H, int F, bool has_dx,
+    bool last_only);
+std::tuple<std::string, int, int, int, int64_t, int> last_gru_launch();
+}  // namespace gordo_gru
+
 // device threshold/statistics kernels (thresholds.hip: K10-K12)
 namespace gordo_thresholds {
 torch::Tensor trail_min_max(torch::Tensor X, int64_t w);
@@ -1126,6 +1141,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("last_scan_launch", &gordo_lstm::last_scan_launch,
           "(family, rows, hf, has_dx, last_only) of this thread's last "
           "scan-kernel launch");
+  // GRU scans (reset_after cell; planned by scan_plan.h's plan_gru)
+  mod.def("gru_seq_fwd", &gordo_gru::gru_seq_fwd, py::arg("xseq"),
+          py::arg("Wx"), py::arg("Wh"), py::arg("bias"),
+          py::arg("store_aux"),
+          "fused GRU forward scan, x-side GEMM inside: {hs, gacts}");
+  mod.def("gru_seq_bwd", &gordo_gru::gru_seq_bwd, py::arg("dSeq"),
+          py::arg("gacts"), py::arg("hs"), py::arg("Wh"),
+          py::arg("last_only"), py::arg("Wx") = py::none(),
+          "fused GRU reverse scan: {dGx, dGh[, dX]}");
+  mod.def("gru_plan", &gordo_gru::gru_plan,
+          "(family, rows, has_dx, last_only, lds_bytes, blocks, error) the "
+          "planner gives a GRU scan request; host only");
+  mod.def("last_gru_launch", &gordo_gru::last_gru_launch,
+          "(family, rows, has_dx, last_only, lds_bytes, blocks) of this "
+          "thread's last GRU scan launch");
   mod.def("grouped_linear_fwd", &grouped_linear_fwd,
           "Y = act(X@W + b) per group (MFMA)");
   mod.def("grouped_linear_bwd_data", &grouped_linear_bwd_data,

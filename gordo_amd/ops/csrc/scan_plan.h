@@ -320,4 +320,80 @@ inline const char* layer_mode(const ScanEnv& env, int G, int B, int H, int F,
   return fused ? "fused" : "two_step";
 }
 
+// ---- GRU scans (gru_seq.hip): a plan of their own, beside plan_scan ----
+// One kernel per direction and no other route: a request outside the
+// geometry is refused, never sent to an LSTM kernel or per timestep.
+constexpr int GRU_GATE_PAD = 4;  // fp32 gate-tile row = 4H + 4 floats
+
+inline size_t lds_gru_fwd(int r, int H, int F) {
+  const size_t ldkc = round32(H + F) + 8;
+  return (size_t)4 * H * ldkc * 2 + (size_t)r * ldkc * 2 +
+         (size_t)r * (4 * H + GRU_GATE_PAD) * 4 + (size_t)4 * H * 4;
+}
+// F = 0 without dX (no Wx tile, no dX staging)
+inline size_t lds_gru_bwd(int r, int H, int F, bool last_only) {
+  const size_t ldg = pad_ldg(4 * H);
+  const size_t tile_row = (size_t)(H / 8) * (last_only ? 5 : 6) * 16;
+  return (size_t)(H + F) * ldg * 2 + (size_t)r * ldg * 2 +
+         (size_t)r * H * 4 + (size_t)r * tile_row + (size_t)r * F * 2;
+}
+
+enum GruFamily { GRU_FWD, GRU_BWD };
+constexpr const char* GRU_FAMILY_NAMES[] = {"gru_fwd", "gru_bwd"};
+
+struct GruRequest {
+  bool fwd;
+  int G, B, T, H, F;  // F = 0 on a backward without dX
+  bool has_dx;        // backward: dX = dGx @ Wx^T inside the scan
+  bool last_only;     // backward: dSeq is the last step's dh only
+};
+
+struct GruPlan {
+  GruFamily family = GRU_FWD;
+  int rows = 0, has_dx = -1, last_only = -1;
+  size_t lds_bytes = 0;
+  int blocks = 0;
+  std::string error;
+  bool ok() const { return error.empty(); }
+  const char* family_name() const { return GRU_FAMILY_NAMES[family]; }
+};
+
+inline GruPlan plan_gru(const GruRequest& q, const ScanEnv& env) {
+  auto refuse_gru = [](std::string msg) {
+    GruPlan p;
+    p.error = std::move(msg);
+    return p;
+  };
+  const bool with_f = q.fwd || q.has_dx;
+  if (q.H < 8 || q.H > 64 || q.H % 8 != 0)
+    return refuse_gru("GRU scan needs H % 8 == 0 and 8 <= H <= 64, got H = " +
+                      std::to_string(q.H));
+  if (with_f && (q.F < 8 || q.F > 128 || q.F % 8 != 0))
+    return refuse_gru("GRU scan needs F % 8 == 0 and 8 <= F <= 128, got F = " +
+                      std::to_string(q.F));
+  // 32-bit per-block store offsets: 64 rows * T * 4H elements
+  if (q.T < 1 || q.T >= (1 << 17))
+    return refuse_gru("GRU scan needs 1 <= T < 2^17, got T = " +
+                      std::to_string(q.T));
+  if (q.G < 1 || q.B < 1) return refuse_gru("GRU scan needs G, B >= 1");
+  const int F = with_f ? q.F : 0;
+  auto need = [&](int r) {
+    return q.fwd ? lds_gru_fwd(r, q.H, F)
+                 : lds_gru_bwd(r, q.H, F, q.last_only);
+  };
+  int rows = pick_rows(env, q.G, q.B);
+  while (rows > 16 && need(rows) > LDS_BUDGET) rows /= 2;
+  if (need(rows) > LDS_BUDGET) return refuse_gru("LDS budget exceeded (gru)");
+  GruPlan p;
+  p.family = q.fwd ? GRU_FWD : GRU_BWD;
+  p.rows = rows;
+  if (!q.fwd) {
+    p.has_dx = q.has_dx;
+    p.last_only = q.last_only;
+  }
+  p.lds_bytes = need(rows);
+  p.blocks = q.G * ceil_div(q.B, rows);
+  return p;
+}
+
 }  // namespace gordo_lstm

@@ -647,6 +647,78 @@ def lstm_seq_bwd_ref(dSeq, gacts, cs, Wh, last_only, *, Wx=None,
 
 
 # ---------------------------------------------------------------------------
+# High-precision oracle of the fused GRU scans (csrc/gru_seq.hip): the
+# Keras 3 cell with reset_after=True, gate order z, r, n, bias rows
+# b[:, 0] (x side) and b[:, 1] (h side). Conventions as above. With
+# ``round_points=True`` values pass through bf16 where the kernels store
+# bf16: h (the one state: it re-enters the recurrence and the convex
+# mix as stored in ``hs``), ``gacts`` = {z, r, n, q}, dGx / dGh (before
+# the carry and dX products, and in the outputs) and dX. The dh carry
+# stays unrounded.
+# ---------------------------------------------------------------------------
+def gru_seq_fwd_ref(x, Wx, Wh, b, *, dtype=torch.float64, round_points=True):
+    """x [G,B,T,F], Wx [G,F,3H], Wh [G,H,3H], b [G,2,3H]; h_{-1} = 0.
+    Returns ``(hs [G,B,T,H], gacts [G,B,T,4H])`` in ``dtype``, gacts
+    being z, r, n and q = h_{t-1} @ Wh_n + b[1]_n."""
+    rnd = _bf16_round if round_points else (lambda t: t)
+    x, Wx, Wh, b = (t.to(dtype) for t in (x, Wx, Wh, b))
+    G, B, T, _ = x.shape
+    H = Wh.shape[1]
+    h = torch.zeros(G, B, H, dtype=dtype)
+    hs, gas = [], []
+    for t in range(T):
+        mx = torch.bmm(x[:, :, t], Wx) + b[:, 0].unsqueeze(1)
+        mh = torch.bmm(h, Wh) + b[:, 1].unsqueeze(1)
+        z = torch.sigmoid(mx[..., :H] + mh[..., :H])
+        r = torch.sigmoid(mx[..., H:2 * H] + mh[..., H:2 * H])
+        q = mh[..., 2 * H:]
+        n = torch.tanh(mx[..., 2 * H:] + r * q)
+        h = rnd(z * h + (1.0 - z) * n)
+        hs.append(h)
+        gas.append(rnd(torch.cat([z, r, n, q], dim=-1)))
+    return torch.stack(hs, 2), torch.stack(gas, 2)
+
+
+def gru_seq_bwd_ref(dSeq, gacts, hs, Wh, last_only, *, Wx=None,
+                    dtype=torch.float64, round_points=True):
+    """Reverse scan: ``(dGx, dGh)`` [G,B,T,3H], the pre-activation gate
+    grads of the kernel side [da_z, da_r, da_n] and of the recurrent
+    side [da_z, da_r, dq], from upstream grads on the h sequence (dSeq
+    [G,B,T,H], or [G,B,H] on h_{T-1} alone when ``last_only``). With
+    ``Wx`` [G,F,3H] also returns dX = dGx @ Wx^T."""
+    rnd = _bf16_round if round_points else (lambda t: t)
+    dSeq, gacts, hs, Wh = (t.to(dtype) for t in (dSeq, gacts, hs, Wh))
+    G, B, T, H4 = gacts.shape
+    H = H4 // 4
+    WhT = Wh.transpose(1, 2)
+    WxT = Wx.to(dtype).transpose(1, 2) if Wx is not None else None
+    carry = torch.zeros(G, B, H, dtype=dtype)
+    dGx, dGh, dX = [None] * T, [None] * T, [None] * T
+    for t in range(T - 1, -1, -1):
+        dh = carry
+        if not last_only:
+            dh = dh + dSeq[:, :, t]
+        elif t == T - 1:
+            dh = dh + dSeq
+        ga = gacts[:, :, t]
+        z, r = ga[..., :H], ga[..., H:2 * H]
+        n, q = ga[..., 2 * H:3 * H], ga[..., 3 * H:]
+        h_prev = hs[:, :, t - 1] if t > 0 else torch.zeros_like(carry)
+        da_n = dh * (1.0 - z) * (1.0 - n * n)
+        da_z = dh * (h_prev - n) * z * (1.0 - z)
+        da_r = da_n * q * r * (1.0 - r)
+        dgx = rnd(torch.cat([da_z, da_r, da_n], dim=-1))
+        dgh = rnd(torch.cat([da_z, da_r, da_n * r], dim=-1))
+        dGx[t], dGh[t] = dgx, dgh
+        carry = torch.bmm(dgh, WhT) + dh * z
+        if WxT is not None:
+            dX[t] = rnd(torch.bmm(dgx, WxT))
+    if WxT is None:
+        return torch.stack(dGx, 2), torch.stack(dGh, 2)
+    return torch.stack(dGx, 2), torch.stack(dGh, 2), torch.stack(dX, 2)
+
+
+# ---------------------------------------------------------------------------
 # Threshold statistics (K10 trail_min_max, K11 windowed_quantile, K12
 # row_quantile; csrc/thresholds.hip). fp64 oracles written from the
 # definitions as plain per-window loops: no pandas rolling, numpy

@@ -37,7 +37,7 @@ import gordo_amd
 from .. import serializer
 from ..builder.build_model import ModelBuilder
 from ..core.base import GordoBaseDataset
-from ..engine.pack import DensePack, LSTMPack
+from ..engine.pack import pack_class
 from ..engine.spec import ModelSpec, normalize_loss, normalize_optimizer
 from ..machine import Machine
 from ..machine.metadata import (
@@ -375,7 +375,7 @@ class PackedFleetBuilder:
         for key, members in groups.items():
             cap = (
                 self.MAX_PACK_LSTM
-                if members[0].spec.model_type == "lstm"
+                if members[0].spec.recurrent
                 else self.MAX_PACK_DENSE
             )
             for s0 in range(0, len(members), cap):
@@ -384,7 +384,7 @@ class PackedFleetBuilder:
 
     # ---- the packed group build -----------------------------------------
     def _pack_cls(self, spec: ModelSpec):
-        return LSTMPack if spec.model_type == "lstm" else DensePack
+        return pack_class(spec)
 
     def _make_pack(self, spec: ModelSpec, group: List[MachinePlan],
                    init_p32=None):
@@ -618,7 +618,7 @@ class PackedFleetBuilder:
     def _fold_cap(self, spec) -> int:
         return (
             self.MAX_CONCURRENT_FOLD_MODELS
-            if spec.model_type == "lstm"
+            if spec.recurrent
             else self.MAX_CONCURRENT_FOLD_MODELS_DENSE
         )
 
