@@ -1501,11 +1501,16 @@ class GRUPack(LSTMPack):
     (reset_after=True, gate order z, r, n, bias [2, 3H]) over the same
     windowed series, parameter store, early stopping, compaction and
     serialization as ``LSTMPack``. Each layer is one ``ops.gru_seq_fwd``
-    launch forward and one ``ops.gru_seq_bwd`` launch backward; the
-    weight grads are the grouped kernels the LSTM uses. There is no
+    call forward and one ``ops.gru_seq_bwd`` call backward; the weight
+    grads are the grouped kernels the LSTM uses. Layers of up to 64
+    units on up to 128 inputs run the fused scans (x-side GEMM and dX
+    inside); wider ones, up to 256 units in multiples of 16 on any
+    number of inputs, run the two-step scans, where those entries make
+    the x-side GEMM before the scan and dX after it. There is no
     per-timestep GRU path: on a GPU, shapes the scan planner refuses
-    (H > 64, F > 128, or GORDO_PAD8=0 with widths that are no multiple
-    of 8) raise at construction with the planner's message."""
+    (H > 256, 64 < H with H % 16 != 0, or GORDO_PAD8=0 with widths that
+    are no multiple of 8) raise at construction with the planner's
+    message."""
 
     def _declare_params(self):
         spec = self.spec

@@ -587,9 +587,10 @@ def lstm_seq_bwd_v3_out(dSeq, gacts, cs, Wh, last_only, dG, act="tanh"):
 
 
 # ---- GRU sequence scans (csrc/gru_seq.hip): the Keras 3 reset_after
-# cell, gate order z, r, n, bias [G, 2, 3H]. One kernel per direction,
-# planned by scan_plan.h's plan_gru(); there is no other GPU route, so a
-# shape the planner refuses raises with its message.
+# cell, gate order z, r, n, bias [G, 2, 3H]. Two kernel pairs, the fused
+# one (H <= 64, F <= 128) and the two-step one (H % 16 == 0 up to 256,
+# any F), planned by scan_plan.h's plan_gru(); there is no other GPU
+# route, so a shape the planner refuses raises with its message.
 
 def _gru_plan(fwd, G, B, T, H, F, has_dx, last_only):
     family, rows, dx, lo, lds, blocks, err = _require_hip().gru_plan(
@@ -612,7 +613,9 @@ def _gru_record(family, rows, has_dx, last_only, lds, blocks) -> dict:
 
 def gru_plan(direction, G, B, T, H, F=0, has_dx=False, last_only=False):
     """What a GRU scan call would launch, without touching the GPU:
-    ``family`` (gru_fwd / gru_bwd), ``rows``, ``has_dx`` / ``last_only``
+    ``family`` (gru_fwd / gru_bwd, or gru_fwd_big / gru_bwd_big for the
+    two-step pair, whose ``has_dx`` is always False: its dX is a GEMM
+    after the scan), ``rows``, ``has_dx`` / ``last_only``
     (backward only, else None), ``lds_bytes`` and ``blocks``; ``None``
     where the planner refuses (``gru_refusal`` has the reason).
     ``direction`` is "fwd" or "bwd"; a backward without dX has F = 0."""
@@ -635,7 +638,10 @@ def gru_seq_fwd(xseq, Wx, Wh, bias, store_aux=True):
     xseq [G,B,T,F], Wx [G,F,3H], Wh [G,H,3H], bias [G,2,3H] ->
     ``(hs [G,B,T,H], gacts [G,B,T,4H])`` with gacts = {z, r, n, q}, or
     ``(hs,)`` with ``store_aux=False`` (inference; same hs bit for
-    bit). CPU tensors take the reference recurrence in their dtype."""
+    bit). Where the planner says ``gru_fwd_big`` the GEMM runs first,
+    as one ``grouped_linear_fwd`` over all B * T rows, and
+    ``gru_seq_fwd_big`` scans its output. CPU tensors take the
+    reference recurrence in their dtype."""
     if _on_gpu(xseq):
         return tuple(_require_hip().gru_seq_fwd(
             xseq, Wx, Wh, bias, bool(store_aux)))
@@ -656,6 +662,23 @@ def gru_seq_bwd(dSeq, gacts, hs, Wh, last_only, Wx=None):
             dSeq, gacts, hs, Wh, bool(last_only), Wx))
     return ref.gru_seq_bwd_ref(dSeq, gacts, hs, Wh, last_only, Wx=Wx,
                                dtype=gacts.dtype, round_points=False)
+
+
+def gru_seq_fwd_big(mx, Wh, bh, store_aux=True):
+    """The two-step GRU forward scan alone (GPU only; H % 16 == 0,
+    16 <= H <= 256): mx [G,B,T,3H] = x @ Wx + b[0], Wh [G,H,3H],
+    bh [G,3H] = b[1] -> what ``gru_seq_fwd`` returns. ``gru_seq_fwd``
+    is ``grouped_linear_fwd`` plus this wherever the planner says
+    ``gru_fwd_big``."""
+    return tuple(_require_hip().gru_seq_fwd_big(mx, Wh, bh, bool(store_aux)))
+
+
+def gru_seq_bwd_big(dSeq, gacts, hs, Wh, last_only):
+    """The two-step GRU reverse scan alone (GPU only): ``(dGx, dGh)``.
+    ``gru_seq_bwd`` adds ``dX = grouped_linear_bwd_data(dGx, Wx)`` when
+    it is given ``Wx``."""
+    return tuple(_require_hip().gru_seq_bwd_big(
+        dSeq, gacts, hs, Wh, bool(last_only)))
 
 
 def anomaly_score(out, y, scale, minv, feat_thr, agg_thr):

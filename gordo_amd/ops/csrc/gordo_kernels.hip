@@ -958,6 +958,16 @@ std::vector<torch::Tensor> lstm_pointwise_bwd(torch::Tensor dh,
 
 }  // namespace
 
+// the GEMMs around the two-step GRU scans, for gru_seq.hip to call
+namespace gordo_gemm {
+torch::Tensor linear_fwd(torch::Tensor X, torch::Tensor W, torch::Tensor b) {
+  return grouped_linear_fwd(X, W, b, ACT_LINEAR);
+}
+torch::Tensor linear_bwd_data(torch::Tensor dZ, torch::Tensor W) {
+  return grouped_linear_bwd_data(dZ, W);
+}
+}  // namespace gordo_gemm
+
 // fused anomaly scoring entry point (anomaly.hip)
 namespace gordo_anomaly {
 std::vector<torch::Tensor> anomaly_score(
@@ -1001,6 +1011,12 @@ std::vector<torch::Tensor> gru_seq_bwd(torch::Tensor dSeq,
                                        torch::Tensor gacts, torch::Tensor hs,
                                        torch::Tensor Wh, bool last_only,
                                        c10::optional<torch::Tensor> Wx);
+std::vector<torch::Tensor> gru_seq_fwd_big(torch::Tensor mx, torch::Tensor Wh,
+                                           torch::Tensor bh, bool store_aux);
+std::vector<torch::Tensor> gru_seq_bwd_big(torch::Tensor dSeq,
+                                           torch::Tensor gacts,
+                                           torch::Tensor hs, torch::Tensor Wh,
+                                           bool last_only);
 std::tuple<std::string, int, int, int, int64_t, int, std::string> gru_plan(
     bool fwd, int G, int B, int T, int H, int F, bool has_dx,
     bool last_only);
@@ -1150,6 +1166,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("gacts"), py::arg("hs"), py::arg("Wh"),
           py::arg("last_only"), py::arg("Wx") = py::none(),
           "fused GRU reverse scan: {dGx, dGh[, dX]}");
+  mod.def("gru_seq_fwd_big", &gordo_gru::gru_seq_fwd_big, py::arg("mx"),
+          py::arg("Wh"), py::arg("bh"), py::arg("store_aux"),
+          "two-step GRU forward scan on mx = x@Wx + b[0]: {hs, gacts}");
+  mod.def("gru_seq_bwd_big", &gordo_gru::gru_seq_bwd_big, py::arg("dSeq"),
+          py::arg("gacts"), py::arg("hs"), py::arg("Wh"),
+          py::arg("last_only"), "two-step GRU reverse scan: {dGx, dGh}");
   mod.def("gru_plan", &gordo_gru::gru_plan,
           "(family, rows, has_dx, last_only, lds_bytes, blocks, error) the "
           "planner gives a GRU scan request; host only");

@@ -22,6 +22,16 @@
 //
 // Geometry: 8 <= H <= 64, H % 8 == 0, 8 <= F <= 128, F % 8 == 0,
 // T < 2^17. One workgroup = 4 waves. docs/kernels.md, "Fused GRU scan".
+//
+// Wider layers (the fused forward keeps 4H weight rows in LDS: 200 KB at
+// (H, F) = (128, 56)) run on a second, two-step pair further down:
+//
+//   gru_seq_fwd_big_kernel : the scan on mx = x @ Wx + b[0], a grouped
+//     GEMM made by the entry; Wh streamed from L2, gate phase in registers.
+//   gru_seq_bwd_big_kernel : the reverse scan to dGx / dGh; dX is a
+//     grouped GEMM made by the entry.
+//
+// Geometry: 16 <= H <= 256, H % 16 == 0, any F % 8 == 0, T < 2^17.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -36,6 +46,12 @@
 #include "scan_plan.h"
 
 #define DEV_INLINE __device__ __forceinline__
+
+// the grouped GEMMs around the two-step scans (gordo_kernels.hip)
+namespace gordo_gemm {
+torch::Tensor linear_fwd(torch::Tensor X, torch::Tensor W, torch::Tensor b);
+torch::Tensor linear_bwd_data(torch::Tensor dZ, torch::Tensor W);
+}  // namespace gordo_gemm
 
 namespace gordo_gru {
 
@@ -515,6 +531,320 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_kernel(
   }
 }
 
+// ===========================================================================
+// Two-step scans (H % 16 == 0, 16 <= H <= 256; the x side is a grouped
+// GEMM outside). Wh stays in global memory (L2-resident after the first
+// step) and is the MFMA *A* operand: 16 hidden units per fragment,
+// K-contiguous 16-byte loads. The B operand is 16 batch rows of the
+// recurrent state from LDS. The 16x16x32 accumulator then gives a lane
+// four CONSECUTIVE hidden units (kslot * 4 ..) of ONE batch row (l15), so
+// the whole gate phase runs on the accumulators with 8-byte accesses: no
+// gate tile, no staging tile. A work item is one 16-unit tile u with the
+// accumulators of all ROWS/16 row blocks: the weight fragments of a k-step
+// are loaded once and used ROWS/16 times. Tiles are dealt round-robin to
+// the four waves (wave index through readfirstlane: every branch around
+// an MFMA is wave-uniform). The state is ping-ponged: a step reads buffer
+// `step & 1` and writes the other, so one barrier per step is enough.
+// Rows past rows_here load from the last live row's addresses, compute,
+// and store nothing.
+//
+// Forward.
+//   mx   [G, B, T, 3H] bf16 = x @ Wx + b[0]
+//   WhT  [G, 3H, Kp]   bf16, Kp = round32(H), zero K tail
+//   bh   [G, 3H]       f32 = b[1]
+//   hs   [G, B, T, H], gacts [G, B, T, 4H] bf16 out (gacts: STORE_AUX)
+// LDS: hS [2][ROWS][Kp + 8] bf16; columns [H, Kp + 8) are zeroed once and
+// never written.
+// ===========================================================================
+DEV_INLINE void unpack4(uint2 p, float (&v)[4]) {
+  v[0] = lo_f(p.x); v[1] = hi_f(p.x); v[2] = lo_f(p.y); v[3] = hi_f(p.y);
+}
+DEV_INLINE uint2 pack4(const float (&v)[4]) {
+  return make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+}
+DEV_INLINE uint2 ld8(const bf16* p) {
+  return *reinterpret_cast<const uint2*>(p);
+}
+DEV_INLINE void st8(bf16* p, uint2 v) { *reinterpret_cast<uint2*>(p) = v; }
+
+template <int ROWS, bool STORE_AUX>
+__global__ __launch_bounds__(256) void gru_seq_fwd_big_kernel(
+    const bf16* __restrict__ mx, const bf16* __restrict__ WhT,
+    const float* __restrict__ bh, bf16* __restrict__ hs,
+    bf16* __restrict__ gacts, int B, int T, int H, int Kp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int H3 = 3 * H, H4 = 4 * H;
+  const int LDH = Kp + 8;
+  bf16* hS = reinterpret_cast<bf16*>(smem);  // [2][ROWS][LDH]
+
+  const int nb = (B + ROWS - 1) / ROWS;
+  const int g = blockIdx.x / nb;
+  const int r0 = (blockIdx.x % nb) * ROWS;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15;
+  const int kslot = lane >> 4;
+
+  const bf16* WTg = WhT + (size_t)g * H3 * Kp;
+  const float* bg = bh + (size_t)g * H3;
+  const bf16* mxg = mx + ((size_t)g * B + r0) * T * H3;
+  bf16* hsg = hs + ((size_t)g * B + r0) * T * H;
+  bf16* gag = gacts + ((size_t)g * B + r0) * T * H4;
+  const int rows_here = min(ROWS, B - r0);
+
+  for (int i = tid; i < 2 * ROWS * LDH / 8; i += 256) {
+    bf16x8 zero = {};
+    *reinterpret_cast<bf16x8*>(&hS[i * 8]) = zero;
+  }
+  __syncthreads();
+
+  constexpr int FM = ROWS / 16;
+  const int NT = H / 16;
+  // this lane's batch row of each row block, clamped for the loads
+  size_t rowT[FM];
+  #pragma unroll
+  for (int fm = 0; fm < FM; ++fm)
+    rowT[fm] = (size_t)min(fm * 16 + l15, rows_here - 1) * T;
+
+  for (int t = 0; t < T; ++t) {
+    const bf16* hc = hS + (size_t)(t & 1) * ROWS * LDH;
+    bf16* hn = hS + (size_t)((t & 1) ^ 1) * ROWS * LDH;
+    for (int u = wid; u < NT; u += 4) {
+      const int unit = u * 16 + kslot * 4;
+      // x-side pre-activations of this step: issued above the K loop,
+      // untouched until the epilogue
+      uint2 xz[FM], xr[FM], xn[FM];
+      #pragma unroll
+      for (int fm = 0; fm < FM; ++fm) {
+        const bf16* p = mxg + (rowT[fm] + t) * H3 + unit;
+        xz[fm] = ld8(p);
+        xr[fm] = ld8(p + H);
+        xn[fm] = ld8(p + 2 * H);
+      }
+      const float4 bz4 = *reinterpret_cast<const float4*>(bg + unit);
+      const float4 br4 = *reinterpret_cast<const float4*>(bg + H + unit);
+      const float4 bq4 = *reinterpret_cast<const float4*>(bg + 2 * H + unit);
+
+      f32x4 az[FM] = {}, ar[FM] = {}, aq[FM] = {};
+      const bf16* wz = WTg + (size_t)(u * 16 + l15) * Kp + kslot * 8;
+      const bf16* wr_ = wz + (size_t)H * Kp;
+      const bf16* wq = wr_ + (size_t)H * Kp;
+      const bf16* hb = hc + l15 * LDH + kslot * 8;
+      for (int kk = 0; kk < Kp; kk += 32) {
+        bf16x8 fz = *reinterpret_cast<const bf16x8*>(wz + kk);
+        bf16x8 fr = *reinterpret_cast<const bf16x8*>(wr_ + kk);
+        bf16x8 fq = *reinterpret_cast<const bf16x8*>(wq + kk);
+        #pragma unroll
+        for (int fm = 0; fm < FM; ++fm) {
+          bf16x8 b = *reinterpret_cast<const bf16x8*>(hb + fm * 16 * LDH + kk);
+          az[fm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fz, b, az[fm], 0, 0, 0);
+          ar[fm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr, b, ar[fm], 0, 0, 0);
+          aq[fm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fq, b, aq[fm], 0, 0, 0);
+        }
+      }
+
+      const float bz[4] = {bz4.x, bz4.y, bz4.z, bz4.w};
+      const float br[4] = {br4.x, br4.y, br4.z, br4.w};
+      const float bq[4] = {bq4.x, bq4.y, bq4.z, bq4.w};
+      #pragma unroll
+      for (int fm = 0; fm < FM; ++fm) {
+        const int row = fm * 16 + l15;
+        float mz[4], mr[4], mn[4], hp[4], z[4], r[4], n[4], q[4], h[4];
+        unpack4(xz[fm], mz);
+        unpack4(xr[fm], mr);
+        unpack4(xn[fm], mn);
+        unpack4(ld8(hc + row * LDH + unit), hp);
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          z[j] = sigmoidf_(mz[j] + az[fm][j] + bz[j]);
+          r[j] = sigmoidf_(mr[j] + ar[fm][j] + br[j]);
+          q[j] = aq[fm][j] + bq[j];
+          n[j] = fast_tanhf_(mn[j] + r[j] * q[j]);
+          h[j] = z[j] * hp[j] + (1.f - z[j]) * n[j];
+        }
+        const uint2 hnew = pack4(h);
+        st8(hn + row * LDH + unit, hnew);
+        if (row < rows_here) {
+          const size_t rt = (size_t)row * T + t;
+          st8(hsg + rt * H + unit, hnew);
+          if (STORE_AUX) {
+            bf16* ga = gag + rt * H4 + unit;
+            st8(ga, pack4(z));
+            st8(ga + H, pack4(r));
+            st8(ga + 2 * H, pack4(n));
+            st8(ga + 3 * H, pack4(q));
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ===========================================================================
+// Two-step backward (reverse-time) scan.
+//   dSeq [G, B, T, H] bf16 (or [G, B, H] with LAST_ONLY)
+//   gacts [G, B, T, 4H], hs [G, B, T, H] bf16;  Wh [G, H, 3H] bf16, native:
+//   its rows are already K-contiguous for carry = dGh @ Wh^T (K = 3H)
+//   dGx, dGh [G, B, T, 3H] bf16 out
+// LDS: dgS [2][ROWS][round32(3H) + 8] bf16 = dGh of the step before, the
+// B operand; columns [3H, ..) are zeroed once and never written. 3H is a
+// multiple of 16, not always of 32: the upper half of the last k-step
+// then meets that zero pad, and its Wh chunk is loaded from a clamped
+// address and selected to zero.
+// The carry never passes through bf16: the MFMA accumulator of step t is
+// joined in registers by dh_{t+1} ⊙ z_{t+1} (dhz, kept per lane across
+// the step in fp32: up to 4 tiles x ROWS/16 blocks x 4 units) and by
+// dSeq_t, and the same lane does step t's gate backward, stores dGx / dGh
+// and writes dGh into the other dgS buffer. The loads of step t
+// {gacts_t, hs_{t-1}, dSeq_t} are issued above its K loop and untouched
+// until the epilogue. With LAST_ONLY dhz starts as dh_last and the loop
+// loads no dSeq.
+// ===========================================================================
+template <int ROWS, bool LAST_ONLY>
+__global__ __launch_bounds__(256) void gru_seq_bwd_big_kernel(
+    const bf16* __restrict__ dSeq, const bf16* __restrict__ gacts,
+    const bf16* __restrict__ hs, const bf16* __restrict__ Wh,
+    bf16* __restrict__ dGx, bf16* __restrict__ dGh, int B, int T, int H) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int H3 = 3 * H, H4 = 4 * H;
+  const int LDG = ((H3 + 31) & ~31) + 8;
+  bf16* dgS = reinterpret_cast<bf16*>(smem);  // [2][ROWS][LDG]
+
+  const int nb = (B + ROWS - 1) / ROWS;
+  const int g = blockIdx.x / nb;
+  const int r0 = (blockIdx.x % nb) * ROWS;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15;
+  const int kslot = lane >> 4;
+
+  const bf16* Whg = Wh + (size_t)g * H * H3;
+  const bf16* gag = gacts + ((size_t)g * B + r0) * T * H4;
+  const bf16* hsg = hs + ((size_t)g * B + r0) * T * H;
+  const bf16* dSg = LAST_ONLY ? dSeq + ((size_t)g * B + r0) * H
+                              : dSeq + ((size_t)g * B + r0) * T * H;
+  bf16* dGxg = dGx + ((size_t)g * B + r0) * T * H3;
+  bf16* dGhg = dGh + ((size_t)g * B + r0) * T * H3;
+  const int rows_here = min(ROWS, B - r0);
+
+  for (int i = tid; i < 2 * ROWS * LDG / 8; i += 256) {
+    bf16x8 zero = {};
+    *reinterpret_cast<bf16x8*>(&dgS[i * 8]) = zero;
+  }
+
+  constexpr int FM = ROWS / 16;
+  constexpr int TS = 4;  // unit tiles per wave: H <= 256
+  const int NT = H / 16;
+  int rowc[FM];
+  #pragma unroll
+  for (int fm = 0; fm < FM; ++fm) rowc[fm] = min(fm * 16 + l15, rows_here - 1);
+
+  float dhz[TS][FM][4];
+  #pragma unroll
+  for (int s = 0; s < TS; ++s) {
+    // tiles past NT are never worked on; their clamped unit keeps the
+    // seed load inside the row
+    const int unit = min(wid + 4 * s, NT - 1) * 16 + kslot * 4;
+    #pragma unroll
+    for (int fm = 0; fm < FM; ++fm) {
+      if (LAST_ONLY) {
+        unpack4(ld8(dSg + (size_t)rowc[fm] * H + unit), dhz[s][fm]);
+      } else {
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) dhz[s][fm][j] = 0.f;
+      }
+    }
+  }
+  __syncthreads();
+
+  for (int t = T - 1; t >= 0; --t) {
+    const int cur = (T - 1 - t) & 1;
+    const bf16* dc = dgS + (size_t)cur * ROWS * LDG;
+    bf16* dn = dgS + (size_t)(cur ^ 1) * ROWS * LDG;
+    const int kend = t == T - 1 ? 0 : H3;  // no carry enters the last step
+    const int tp = max(t - 1, 0);          // hs_{t-1}; taken as 0 at t = 0
+    #pragma unroll
+    for (int s = 0; s < TS; ++s) {
+      const int u = wid + 4 * s;
+      if (u < NT) {  // wave-uniform
+        const int unit = u * 16 + kslot * 4;
+        uint2 gz[FM], gr[FM], gn[FM], gq[FM], hv[FM], dv[FM];
+        #pragma unroll
+        for (int fm = 0; fm < FM; ++fm) {
+          const size_t rT = (size_t)rowc[fm] * T;
+          const bf16* ga = gag + (rT + t) * H4 + unit;
+          gz[fm] = ld8(ga);
+          gr[fm] = ld8(ga + H);
+          gn[fm] = ld8(ga + 2 * H);
+          gq[fm] = ld8(ga + 3 * H);
+          hv[fm] = ld8(hsg + (rT + tp) * H + unit);
+          if (!LAST_ONLY) dv[fm] = ld8(dSg + (rT + t) * H + unit);
+        }
+
+        f32x4 acc[FM] = {};
+        const bf16* wrow = Whg + (size_t)(u * 16 + l15) * H3;
+        const bf16* db = dc + l15 * LDG + kslot * 8;
+        for (int kk = 0; kk < kend; kk += 32) {
+          const int k = kk + kslot * 8;
+          bf16x8 a = *reinterpret_cast<const bf16x8*>(wrow + min(k, H3 - 8));
+          const bf16x8 zero = {};
+          a = k < H3 ? a : zero;
+          #pragma unroll
+          for (int fm = 0; fm < FM; ++fm) {
+            bf16x8 b =
+                *reinterpret_cast<const bf16x8*>(db + fm * 16 * LDG + kk);
+            acc[fm] =
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[fm], 0, 0, 0);
+          }
+        }
+
+        #pragma unroll
+        for (int fm = 0; fm < FM; ++fm) {
+          const int row = fm * 16 + l15;
+          float z[4], r[4], n[4], q[4], hp[4], ds[4];
+          float daz[4], dar[4], dan[4], dq[4];
+          unpack4(gz[fm], z);
+          unpack4(gr[fm], r);
+          unpack4(gn[fm], n);
+          unpack4(gq[fm], q);
+          unpack4(hv[fm], hp);
+          if (!LAST_ONLY) unpack4(dv[fm], ds);
+          #pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float dh = acc[fm][j] + dhz[s][fm][j];
+            if (!LAST_ONLY) dh += ds[j];
+            const float hprev = t > 0 ? hp[j] : 0.f;
+            dan[j] = dh * (1.f - z[j]) * (1.f - n[j] * n[j]);
+            daz[j] = dh * (hprev - n[j]) * z[j] * (1.f - z[j]);
+            dar[j] = dan[j] * q[j] * r[j] * (1.f - r[j]);
+            dq[j] = dan[j] * r[j];
+            dhz[s][fm][j] = dh * z[j];
+          }
+          const uint2 pz = pack4(daz), pr = pack4(dar), pn = pack4(dan),
+                      pq = pack4(dq);
+          bf16* dg = dn + row * LDG + unit;
+          st8(dg, pz);
+          st8(dg + H, pr);
+          st8(dg + 2 * H, pq);
+          if (row < rows_here) {
+            const size_t o = ((size_t)row * T + t) * H3 + unit;
+            st8(dGxg + o, pz);
+            st8(dGxg + o + H, pr);
+            st8(dGxg + o + 2 * H, pn);
+            st8(dGhg + o, pz);
+            st8(dGhg + o + H, pr);
+            st8(dGhg + o + 2 * H, pq);
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
@@ -588,6 +918,67 @@ inline void check_shape(const torch::Tensor& t, std::vector<int64_t> shape,
               " has the wrong shape or device for this GRU scan");
 }
 
+// mx [G,B,T,3H] = x @ Wx + b[0]; Wh [G,H,3H]; bh [G,3H] = b[1]
+// -> {hs, gacts} ({hs} without store_aux): the two-step forward scan alone
+std::vector<torch::Tensor> gru_seq_fwd_big(torch::Tensor mx, torch::Tensor Wh,
+                                           torch::Tensor bh, bool store_aux) {
+  TORCH_CHECK(mx.is_cuda() && mx.dim() == 4, "mx must be [G,B,T,3H] on GPU");
+  TORCH_CHECK(Wh.dim() == 3, "Wh must be [G,H,3H]");
+  auto mc = as_bf16(mx);
+  const int G = mc.size(0), B = mc.size(1), T = mc.size(2);
+  const int H = Wh.size(1), H3 = 3 * H;
+  check_shape(mx, {G, B, T, H3}, "mx");
+  check_shape(Wh, {G, H, H3}, "Wh");
+  check_shape(bh, {G, H3}, "bh");
+  const GruPlan p = planned({true, G, B, T, H, 0, false, false, true});
+  // K-contiguous rows with a zero K tail up to the MFMA K step
+  const int Kp = gordo_lstm::round32(H);
+  auto WhT = torch::zeros({G, H3, Kp}, mc.options());
+  WhT.narrow(2, 0, H).copy_(Wh.to(torch::kBFloat16).transpose(1, 2));
+  auto bf = bh.to(torch::kFloat32).contiguous();
+  auto hs = torch::empty({G, B, T, H}, mc.options());
+  auto gacts = store_aux ? torch::empty({G, B, T, 4 * H}, mc.options())
+                         : torch::empty({1}, mc.options());
+  pick_tile(p.rows, [&](auto R) {
+    pick(store_aux, [&](auto AUX) {
+      launch(gru_seq_fwd_big_kernel<decltype(R)::value, decltype(AUX)::value>,
+             p, rd(mc), rd(WhT), bf.data_ptr<float>(), wr(hs), wr(gacts), B,
+             T, H, Kp);
+    });
+  });
+  if (store_aux) return {hs, gacts};
+  return {hs};
+}
+
+// dSeq [G,B,T,H] (or [G,B,H] with last_only); gacts [G,B,T,4H];
+// hs [G,B,T,H]; Wh [G,H,3H] -> {dGx, dGh}: the two-step reverse scan alone
+std::vector<torch::Tensor> gru_seq_bwd_big(torch::Tensor dSeq,
+                                           torch::Tensor gacts,
+                                           torch::Tensor hs, torch::Tensor Wh,
+                                           bool last_only) {
+  TORCH_CHECK(gacts.is_cuda() && gacts.dim() == 4,
+              "gacts must be [G,B,T,4H] on GPU");
+  auto gc = as_bf16(gacts);
+  const int G = gc.size(0), B = gc.size(1), T = gc.size(2), H4 = gc.size(3);
+  const int H = H4 / 4, H3 = 3 * H;
+  TORCH_CHECK(H4 == 4 * H, "gacts must be [G,B,T,4H]");
+  check_shape(hs, {G, B, T, H}, "hs");
+  check_shape(Wh, {G, H, H3}, "Wh");
+  if (last_only) check_shape(dSeq, {G, B, H}, "dSeq");
+  else check_shape(dSeq, {G, B, T, H}, "dSeq");
+  const GruPlan p = planned({false, G, B, T, H, 0, false, last_only, true});
+  auto dc = as_bf16(dSeq), hc = as_bf16(hs), Whc = as_bf16(Wh);
+  auto dGx = torch::empty({G, B, T, H3}, gc.options());
+  auto dGh = torch::empty({G, B, T, H3}, gc.options());
+  pick_tile(p.rows, [&](auto R) {
+    pick(last_only, [&](auto LO) {
+      launch(gru_seq_bwd_big_kernel<decltype(R)::value, decltype(LO)::value>,
+             p, rd(dc), rd(gc), rd(hc), rd(Whc), wr(dGx), wr(dGh), B, T, H);
+    });
+  });
+  return {dGx, dGh};
+}
+
 // xseq [G,B,T,F]; Wx [G,F,3H]; Wh [G,H,3H]; bias [G,2,3H] -> {hs, gacts}
 // ({hs} without store_aux)
 std::vector<torch::Tensor> gru_seq_fwd(torch::Tensor xseq, torch::Tensor Wx,
@@ -603,6 +994,12 @@ std::vector<torch::Tensor> gru_seq_fwd(torch::Tensor xseq, torch::Tensor Wx,
   check_shape(Wx, {G, F, 3 * H}, "Wx");
   check_shape(bias, {G, 2, 3 * H}, "bias");
   const GruPlan p = planned({true, G, B, T, H, F, false, false});
+  if (p.big()) {  // two-step: one GEMM over all B * T rows, then the scan
+    auto mx = gordo_gemm::linear_fwd(xc.view({G, B * T, F}), Wx,
+                                     bias.select(1, 0));
+    return gru_seq_fwd_big(mx.view({G, B, T, 3 * H}), Wh, bias.select(1, 1),
+                           store_aux);
+  }
   auto Whc = Wh.to(torch::kBFloat16), Wxc = Wx.to(torch::kBFloat16);
   // [G, Kc, 4H] with the zero blocks of n_x / n_h, then K-contiguous
   auto W4 = torch::zeros({G, H + F, H4}, xc.options());
@@ -650,6 +1047,14 @@ std::vector<torch::Tensor> gru_seq_bwd(torch::Tensor dSeq,
   else check_shape(dSeq, {G, B, T, H}, "dSeq");
   if (has_dx) check_shape(*Wx, {G, F, H3}, "Wx");
   const GruPlan p = planned({false, G, B, T, H, F, has_dx, last_only});
+  if (p.big()) {  // two-step: the scan, then dX as one GEMM
+    auto out = gru_seq_bwd_big(dSeq, gacts, hs, Wh, last_only);
+    if (has_dx)
+      out.push_back(
+          gordo_gemm::linear_bwd_data(out[0].view({G, B * T, H3}), *Wx)
+              .view({G, B, T, F}));
+    return out;
+  }
   auto dc = as_bf16(dSeq), hc = as_bf16(hs), Whc = as_bf16(Wh);
   auto Wxc = has_dx ? as_bf16(*Wx) : torch::Tensor();
   auto dGx = torch::empty({G, B, T, H3}, gc.options());

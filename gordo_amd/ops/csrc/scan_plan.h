@@ -321,8 +321,8 @@ inline const char* layer_mode(const ScanEnv& env, int G, int B, int H, int F,
 }
 
 // ---- GRU scans (gru_seq.hip): a plan of their own, beside plan_scan ----
-// One kernel per direction and no other route: a request outside the
-// geometry is refused, never sent to an LSTM kernel or per timestep.
+// Two kernel pairs and no other route: a request outside both
+// geometries is refused, never sent to an LSTM kernel or per timestep.
 constexpr int GRU_GATE_PAD = 4;  // fp32 gate-tile row = 4H + 4 floats
 
 inline size_t lds_gru_fwd(int r, int H, int F) {
@@ -338,14 +338,26 @@ inline size_t lds_gru_bwd(int r, int H, int F, bool last_only) {
          (size_t)r * H * 4 + (size_t)r * tile_row + (size_t)r * F * 2;
 }
 
-enum GruFamily { GRU_FWD, GRU_BWD };
-constexpr const char* GRU_FAMILY_NAMES[] = {"gru_fwd", "gru_bwd"};
+// two-step family (H up to 256, any F): Wh stays in global memory, the
+// only LDS state is the ping-ponged MFMA B operand: h [2][r][round32(H)+8]
+// forward, dGh [2][r][round32(3H)+8] backward (bf16 both)
+inline size_t lds_gru_fwd_big(int r, int H) {
+  return (size_t)2 * r * (round32(H) + 8) * 2;
+}
+inline size_t lds_gru_bwd_big(int r, int H, bool /*last_only*/) {
+  return (size_t)2 * r * (round32(3 * H) + 8) * 2;
+}
+
+enum GruFamily { GRU_FWD, GRU_BWD, GRU_FWD_BIG, GRU_BWD_BIG };
+constexpr const char* GRU_FAMILY_NAMES[] = {"gru_fwd", "gru_bwd",
+                                            "gru_fwd_big", "gru_bwd_big"};
 
 struct GruRequest {
   bool fwd;
   int G, B, T, H, F;  // F = 0 on a backward without dX
-  bool has_dx;        // backward: dX = dGx @ Wx^T inside the scan
+  bool has_dx;        // backward: dX = dGx @ Wx^T (inside the fused scan)
   bool last_only;     // backward: dSeq is the last step's dh only
+  bool big = false;   // the scan-only entries: the two-step family or none
 };
 
 struct GruPlan {
@@ -355,22 +367,40 @@ struct GruPlan {
   int blocks = 0;
   std::string error;
   bool ok() const { return error.empty(); }
+  bool big() const { return family == GRU_FWD_BIG || family == GRU_BWD_BIG; }
   const char* family_name() const { return GRU_FAMILY_NAMES[family]; }
 };
 
+// The fused pair serves what it served before the two-step pair came;
+// what it refuses for its H or F range goes two-step when H % 16 == 0,
+// 16 <= H <= 256 and F % 8 == 0, F >= 8 (a 16-unit MFMA tile must not
+// straddle two gate blocks). A two-step backward never has dX inside.
 inline GruPlan plan_gru(const GruRequest& q, const ScanEnv& env) {
   auto refuse_gru = [](std::string msg) {
     GruPlan p;
     p.error = std::move(msg);
     return p;
   };
-  const bool with_f = q.fwd || q.has_dx;
-  if (q.H < 8 || q.H > 64 || q.H % 8 != 0)
-    return refuse_gru("GRU scan needs H % 8 == 0 and 8 <= H <= 64, got H = " +
-                      std::to_string(q.H));
-  if (with_f && (q.F < 8 || q.F > 128 || q.F % 8 != 0))
-    return refuse_gru("GRU scan needs F % 8 == 0 and 8 <= F <= 128, got F = " +
-                      std::to_string(q.F));
+  const bool with_f = (q.fwd || q.has_dx) && !q.big;
+  const bool fused_h = q.H >= 8 && q.H <= 64 && q.H % 8 == 0;
+  const bool fused_f = !with_f || (q.F >= 8 && q.F <= 128 && q.F % 8 == 0);
+  const bool big_h = q.H >= 16 && q.H <= 256 && q.H % 16 == 0;
+  const bool big_f = !with_f || (q.F >= 8 && q.F % 8 == 0);
+  const bool fused = !q.big && fused_h && fused_f;
+  if (!fused && !(big_h && big_f)) {
+    if (q.big)
+      return refuse_gru(
+          "two-step GRU scan needs H % 16 == 0 and 16 <= H <= 256, got H = " +
+          std::to_string(q.H));
+    if (!fused_h)
+      return refuse_gru(
+          "GRU scan needs H % 8 == 0 and 8 <= H <= 64 (fused) or H % 16 == 0 "
+          "and 16 <= H <= 256 (two-step), got H = " + std::to_string(q.H));
+    return refuse_gru(
+        "GRU scan needs F % 8 == 0 and 8 <= F <= 128 (fused) or F % 8 == 0, "
+        "F >= 8 with H % 16 == 0, H >= 16 (two-step), got F = " +
+        std::to_string(q.F) + " at H = " + std::to_string(q.H));
+  }
   // 32-bit per-block store offsets: 64 rows * T * 4H elements
   if (q.T < 1 || q.T >= (1 << 17))
     return refuse_gru("GRU scan needs 1 <= T < 2^17, got T = " +
@@ -378,6 +408,9 @@ inline GruPlan plan_gru(const GruRequest& q, const ScanEnv& env) {
   if (q.G < 1 || q.B < 1) return refuse_gru("GRU scan needs G, B >= 1");
   const int F = with_f ? q.F : 0;
   auto need = [&](int r) {
+    if (!fused)
+      return q.fwd ? lds_gru_fwd_big(r, q.H)
+                   : lds_gru_bwd_big(r, q.H, q.last_only);
     return q.fwd ? lds_gru_fwd(r, q.H, F)
                  : lds_gru_bwd(r, q.H, F, q.last_only);
   };
@@ -385,10 +418,11 @@ inline GruPlan plan_gru(const GruRequest& q, const ScanEnv& env) {
   while (rows > 16 && need(rows) > LDS_BUDGET) rows /= 2;
   if (need(rows) > LDS_BUDGET) return refuse_gru("LDS budget exceeded (gru)");
   GruPlan p;
-  p.family = q.fwd ? GRU_FWD : GRU_BWD;
+  p.family = fused ? (q.fwd ? GRU_FWD : GRU_BWD)
+                   : (q.fwd ? GRU_FWD_BIG : GRU_BWD_BIG);
   p.rows = rows;
   if (!q.fwd) {
-    p.has_dx = q.has_dx;
+    p.has_dx = fused && q.has_dx;
     p.last_only = q.last_only;
   }
   p.lds_bytes = need(rows);
