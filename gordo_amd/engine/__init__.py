@@ -1,5 +1,6 @@
 from .spec import ModelSpec, LayerSpec
-from .pack import DensePack, LSTMPack, GRUPack, BasePack, pack_class
+from .pack import (DensePack, LSTMPack, GRUPack, Conv1DPack, BasePack,
+                   pack_class)
 
-__all__ = ["ModelSpec", "LayerSpec", "DensePack", "LSTMPack", "GRUPack", "BasePack",
+__all__ = ["ModelSpec", "LayerSpec", "DensePack", "LSTMPack", "GRUPack", "Conv1DPack", "BasePack",
            "pack_class"]

@@ -1641,6 +1641,163 @@ class GRUPack(LSTMPack):
         return loss
 
 
+class Conv1DPack(LSTMPack):
+    """Grouped convolutional window model: a stack of Keras ``Conv1D``
+    layers (strides 1, ``same`` or ``causal``, dilated) over the lookback
+    window, flattened into one Dense, over the same windowed series,
+    parameter store, early stopping, compaction and serialization as
+    ``LSTMPack``. Each layer is one ``ops.conv1d_fwd`` call forward and,
+    backward, ``ops.act_l1_bwd``, ``ops.conv1d_wgrad`` and (for every
+    layer but the bottom one) ``ops.conv1d_bwd_data``; the head runs on
+    the ``[G, B, T*C]`` view of the last layer's output.
+
+    Zero-padded channels are inert for tanh, relu and linear layers
+    (act(0) = 0 and their weight rows, columns and bias stay 0, see
+    ``pad_enabled``). sigmoid(0) = 0.5 is not: a pack with a sigmoid
+    layer whose width would actually be padded keeps its logical dims.
+    On a GPU, shapes the Conv1D planner refuses (channels that are no
+    multiple of 8 after that, more than 128 channels, kernel_size > 8,
+    (kernel_size - 1) * dilation > 64) raise at construction with the
+    planner's message."""
+
+    def _declare_params(self):
+        spec = self.spec
+        conv_layers = [l for l in spec.layers if l.kind == "conv1d"]
+        dense_layers = [l for l in spec.layers if l.kind == "dense"]
+        assert len(dense_layers) == 1 and len(conv_layers) + 1 == len(
+            spec.layers) and conv_layers, "Conv1D spec must be [Conv1D..., Dense]"
+        if self.pad8 and any(
+            l.activation == "sigmoid" and l.units % 8 for l in conv_layers
+        ):
+            self.pad8 = False
+            self._pad = lambda n: int(n)
+        p = self._pad
+        T = max(int(spec.lookback_window), 1)
+        # PHYSICAL / logical (cin, cout, k, dilation, padding, activation)
+        self.conv_meta = []
+        self.conv_meta_logical = []
+        cin_l = self._logical_in = spec.n_features
+        for i, layer in enumerate(conv_layers):
+            cout_l, k, d = layer.units, layer.kernel_size, layer.dilation
+            cin, cout = p(cin_l), p(cout_l)
+            if self.device.type == "cuda":
+                self._check_planned(cin, cout, k, d, layer.padding, T,
+                                    has_dx=i > 0)
+            regs = layer.weight_regs()
+            self.store.declare(f"Wc{i}", (self.G, k, cin, cout),
+                               logical=(self.G, k, cin_l, cout_l),
+                               reg=regs["kernel"])
+            self.store.declare(f"bc{i}", (self.G, cout),
+                               logical=(self.G, cout_l), reg=regs["bias"])
+            self.conv_meta.append(
+                (cin, cout, k, d, layer.padding, layer.activation))
+            self.conv_meta_logical.append(
+                (cin_l, cout_l, k, d, layer.padding, layer.activation))
+            cin_l = cout_l
+        out_layer = dense_layers[0]
+        out_l = self._logical_out = out_layer.units
+        C_l, C, out = cin_l, p(cin_l), p(out_l)
+        self.dense_meta = (T * C, out, out_layer.activation)
+        self.dense_meta_logical = (T * C_l, out_l, out_layer.activation)
+        out_regs = out_layer.weight_regs()
+        # Flatten is row-major over (t, c): the head's rows are [T, C]
+        self.store.declare("Wd", (self.G, T * C, out),
+                           logical=(self.G, T * C_l, out_l),
+                           reg=out_regs["kernel"])
+        self.store.declare("bd", (self.G, out), logical=(self.G, out_l),
+                           reg=out_regs["bias"])
+        if C != C_l or out != out_l:
+            def extract(arr):
+                return arr.reshape(T, C, out)[:, :C_l, :out_l].reshape(
+                    T * C_l, out_l).copy()
+
+            def insert(view, t):
+                view.zero_()
+                view.view(T, C, out)[:, :C_l, :out_l].copy_(
+                    t.reshape(T, C_l, out_l))
+
+            self._extractors["Wd"] = (extract, insert)
+
+    def _check_planned(self, cin, cout, k, d, padding, T, has_dx):
+        """Raise with the Conv1D planner's message where it refuses a
+        layer (the batch size plays no part in a refusal)."""
+        entries = ("fwd", "wgrad") + (("bwd_data",) if has_dx else ())
+        for entry in entries:
+            why = ops.conv1d_refusal(entry, self.G, 1, T, cin, cout, k, d,
+                                     padding)
+            if why:
+                raise ValueError(
+                    f"Conv1D layer ({cin} -> {cout}, kernel_size {k}, "
+                    f"dilation {d}) has no kernel: {why}"
+                )
+
+    def _init_weights(self):
+        # as Keras: glorot-uniform kernels with fan_in = k * Cin and
+        # fan_out = k * Cout, zero biases; logical draws in the CPU
+        # pack's RNG order, then written into the padded tensors
+        for g in range(self.G):
+            gen = torch.Generator().manual_seed(int(self.seeds[g]) & 0x7FFFFFFF)
+            for i, (cin_l, cout_l, k, *_r) in enumerate(self.conv_meta_logical):
+                limit = math.sqrt(6.0 / (k * cin_l + k * cout_l))
+                w = (torch.rand((k, cin_l, cout_l), generator=gen,
+                                dtype=torch.float32) * 2 - 1) * limit
+                self._insert_logical(
+                    f"Wc{i}", self.store.views[f"Wc{i}"][g], w.numpy()
+                )
+            fin_l, fout_l, _act = self.dense_meta_logical
+            wd = _glorot_uniform((fin_l, fout_l), gen)
+            self._insert_logical("Wd", self.store.views["Wd"][g], wd.numpy())
+
+    def _scan_modes(self, B: Optional[int] = None) -> List[str]:
+        return ["conv"] * len(self.conv_meta)
+
+    def _forward_seq(self, Xw: torch.Tensor, keep: bool, modes=None):
+        """Xw: [G, B, T, F]. Returns (y, cache): per layer its input and
+        output sequence, then the head's input and output."""
+        seq = Xw
+        cache = []
+        for i, (_ci, _co, _k, d, padding, act) in enumerate(self.conv_meta):
+            out = ops.conv1d_fwd(
+                seq, self.store.cviews[f"Wc{i}"], self.store.views[f"bc{i}"],
+                act, padding, d,
+            )
+            if keep:
+                cache.append(dict(seq_in=seq, out=out))
+            seq = out
+        G, B, T, C = seq.shape
+        flat = seq.reshape(G, B, T * C)  # a view: Flatten costs nothing
+        _fin, _fout, act = self.dense_meta
+        y = ops.grouped_linear_fwd(
+            flat, self.store.cviews["Wd"], self.store.views["bd"], act
+        )
+        if keep:
+            cache.append(dict(h_last=flat, y=y))
+        return y, cache
+
+    def train_batch(self, Xw, Tb) -> torch.Tensor:
+        Xw, Tb = self._pad_io(Xw, Tb)
+        G, B, T, _ = Xw.shape
+        y, cache = self._forward_seq(Xw, keep=True)
+        loss, dY, self.last_correct = self._loss_bwd(y, Tb)
+        dA = self._head_bwd(cache[-1], dY).view(G, B, T, -1)
+        for i in range(len(self.conv_meta) - 1, -1, -1):
+            _ci, _co, k, d, padding, act = self.conv_meta[i]
+            lc = cache[i]
+            dZ = ops.act_l1_bwd(dA, lc["out"], act, 0.0)
+            dW, db = ops.conv1d_wgrad(lc["seq_in"], dZ, k, padding, d)
+            self.store.gviews[f"Wc{i}"].copy_(dW)
+            self.store.gviews[f"bc{i}"].copy_(db)
+            cache[i] = None  # free this layer's cache before descending
+            dA = (
+                ops.conv1d_bwd_data(dZ, self.store.cviews[f"Wc{i}"], padding, d)
+                if i > 0 else None
+            )
+            del lc, dZ
+        self.store.optimizer_step()
+        return loss
+
+
 def pack_class(spec: ModelSpec):
     """The pack that trains a spec: by its model_type."""
-    return {"lstm": LSTMPack, "gru": GRUPack}.get(spec.model_type, DensePack)
+    return {"lstm": LSTMPack, "gru": GRUPack, "conv1d": Conv1DPack}.get(
+        spec.model_type, DensePack)

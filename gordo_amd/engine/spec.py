@@ -298,7 +298,7 @@ def parse_weight_regularizer(reg_def: Any, owner: str = "regularizer"
 
 @dataclass
 class LayerSpec:
-    kind: str  # "dense" | "lstm" | "gru"
+    kind: str  # "dense" | "lstm" | "gru" | "conv1d"
     units: int
     activation: str = "tanh"
     l1_activity: float = 0.0  # L1 activity regularizer weight (dense)
@@ -312,12 +312,36 @@ class LayerSpec:
     bias_l2: float = 0.0
     recurrent_l1: float = 0.0
     recurrent_l2: float = 0.0
+    # conv1d only (units = filters; strides 1, groups 1, channels last)
+    kernel_size: int = 1
+    dilation: int = 1
+    padding: str = "same"  # "same" | "causal"
 
     def __post_init__(self):
         for name in _REG_FIELDS:
             setattr(self, name, _reg_coefficient(
                 f"{self.kind} layer", name, getattr(self, name)
             ))
+        if self.kind == "conv1d":
+            act = "linear" if self.activation is None else self.activation
+            if not (isinstance(act, str) and act.lower() in LSTM_ACTIVATIONS):
+                raise ValueError(
+                    f"Unsupported Conv1D activation {self.activation!r}; "
+                    f"supported: {sorted(LSTM_ACTIVATIONS)}"
+                )
+            self.activation = act.lower()
+            self.kernel_size, self.dilation = (
+                int(self.kernel_size), int(self.dilation))
+            if self.kernel_size < 1 or self.dilation < 1:
+                raise ValueError(
+                    "Conv1D kernel_size and dilation_rate must be >= 1, got "
+                    f"{self.kernel_size} and {self.dilation}"
+                )
+            if self.padding not in ("same", "causal"):
+                raise ValueError(
+                    f"Unsupported Conv1D padding {self.padding!r}: the "
+                    "engine runs 'same' and 'causal'"
+                )
         if self.kind not in ("lstm", "gru") and (
             self.recurrent_l1 or self.recurrent_l2
         ):
@@ -331,6 +355,8 @@ class LayerSpec:
         self.__dict__.update(state)
         for name in _REG_FIELDS:
             self.__dict__.setdefault(name, 0.0)
+        for name, default in _CONV_FIELDS:
+            self.__dict__.setdefault(name, default)
 
     def weight_regs(self) -> Dict[str, Tuple[float, float]]:
         """(l1, l2) per tensor role: kernel, recurrent, bias."""
@@ -348,18 +374,26 @@ class LayerSpec:
         return cls(**d)
 
 
+# LayerSpec fields only a conv1d layer sets, with their defaults
+_CONV_FIELDS = (("kernel_size", 1), ("dilation", 1), ("padding", "same"))
+
+
 def _layer_dict(d: Dict[str, Any]) -> Dict[str, Any]:
-    """A layer's dict without the regularizer fields when all are zero:
-    an unregularized layer's dict is what it was before they existed."""
+    """A layer's dict without the regularizer fields when all are zero,
+    and without the conv1d fields on every other layer: such a layer's
+    dict is what it was before those fields existed."""
     if not any(d[name] for name in _REG_FIELDS):
         for name in _REG_FIELDS:
+            del d[name]
+    if d["kind"] != "conv1d":
+        for name, _default in _CONV_FIELDS:
             del d[name]
     return d
 
 
 @dataclass
 class ModelSpec:
-    model_type: str  # "feedforward" | "lstm" | "gru"
+    model_type: str  # "feedforward" | "lstm" | "gru" | "conv1d"
     n_features: int
     n_features_out: int
     layers: List[LayerSpec] = field(default_factory=list)
@@ -416,8 +450,10 @@ class ModelSpec:
 
     @property
     def recurrent(self) -> bool:
-        """A windowed stack of LSTM or GRU layers under one Dense."""
-        return self.model_type in ("lstm", "gru")
+        """A stack over lookback windows under one Dense: LSTM or GRU
+        layers, or Conv1D layers (no recurrence there, but the same
+        windowed series, caches and pack caps)."""
+        return self.model_type in ("lstm", "gru", "conv1d")
 
     # ---- shape helpers -------------------------------------------------
     def dense_dims(self) -> List[tuple]:
@@ -469,6 +505,9 @@ class ModelSpec:
                 # per tensor, not per model: differently regularized
                 # models do not share a pack
                 + tuple(getattr(l, name) for name in _REG_FIELDS)
+                # other layers' keys stay what they were
+                + (tuple(getattr(l, name) for name, _ in _CONV_FIELDS)
+                   if l.kind == "conv1d" else ())
                 for l in self.layers
             ),
             self.lookback_window,

@@ -379,7 +379,8 @@ class KerasAutoEncoder(KerasBaseEstimator, TransformerMixin):
 
 class KerasRawModelRegressor(KerasAutoEncoder):
     """Build a model from a raw definition — ``kind`` is a dict with a
-    ``spec:`` (a Sequential of Dense and/or LSTM layers) and an
+    ``spec:`` (a Sequential of Dense layers, of LSTM or GRU layers under
+    one Dense, or of Conv1D layers flattened into one Dense) and an
     optional ``compile:`` section (plain strings or nested
     loss/optimizer dicts with kwargs), exactly the reference's
     raw-config shape (models.py:401-460). LSTM raw specs run through
@@ -477,8 +478,9 @@ def _parse_raw_spec(
     """Parse a keras-like raw Sequential spec into a ModelSpec.
 
     Supported layer families (everything the device engine runs):
-    ``Dense`` stacks, and ``LSTM`` or ``GRU`` stacks ending in one
-    Dense output layer (the reference's raw path accepts arbitrary keras specs,
+    ``Dense`` stacks, ``LSTM`` or ``GRU`` stacks ending in one Dense
+    output layer, and ``[Conv1D..., Flatten, Dense]`` window models
+    (the reference's raw path accepts arbitrary keras specs,
     models.py:401-460; LSTM-in-raw-spec was a round-1 gap — VERDICT
     next-round #8). ``Dropout``/``Activation`` wrappers raise with a
     clear message rather than being silently ignored."""
@@ -490,7 +492,8 @@ def _parse_raw_spec(
     body = spec_def[seq_key] or {}
     layers_def = body.get("layers", [])
     layers: List[LayerSpec] = []
-    has_lstm = has_gru = False
+    has_lstm = has_gru = has_conv = False
+    n_flatten = 0
     for layer_def in layers_def:
         if not (isinstance(layer_def, dict) and len(layer_def) == 1):
             raise ValueError(f"Unparsable layer definition {layer_def!r}")
@@ -528,6 +531,22 @@ def _parse_raw_spec(
         elif lname == "GRU":
             has_gru = True
             layers.append(_parse_raw_gru(lkw, n_features_out))
+        elif lname == "Conv1D":
+            has_conv = True
+            if n_flatten:
+                raise ValueError(
+                    "raw Conv1D specs must be [Conv1D..., Flatten, Dense]: "
+                    "a Conv1D layer after Flatten is unsupported"
+                )
+            layers.append(_parse_raw_conv1d(lkw))
+        elif lname == "Flatten" and has_conv:
+            data_format = lkw.get("data_format")
+            if data_format not in (None, "channels_last"):
+                raise ValueError(
+                    f"Unsupported Flatten data_format {data_format!r}: the "
+                    "engine's windows are channels_last"
+                )
+            n_flatten += 1
         else:
             raise ValueError(
                 f"Unsupported layer {lk!r} in raw spec (Dense/LSTM)"
@@ -535,6 +554,46 @@ def _parse_raw_spec(
     if not layers:
         raise ValueError("raw spec contains no layers")
     loss, loss_kw, optimizer, opt_kw = _parse_raw_compile(compile_def or {})
+    if has_conv:
+        if has_lstm or has_gru:
+            raise ValueError(
+                "raw Conv1D specs must be [Conv1D..., Flatten, Dense]: a "
+                "stack that mixes Conv1D with LSTM or GRU layers is "
+                "unsupported"
+            )
+        n_dense = sum(l.kind == "dense" for l in layers)
+        if n_dense > 1:
+            raise ValueError(
+                "raw Conv1D specs must be [Conv1D..., Flatten, Dense]: more "
+                "than one Dense layer is unsupported"
+            )
+        if n_flatten != 1:
+            raise ValueError(
+                "raw Conv1D specs must be [Conv1D..., Flatten, Dense]: "
+                + ("the Flatten layer is missing" if not n_flatten
+                   else "more than one Flatten layer")
+            )
+        if n_dense != 1 or layers[-1].kind != "dense":
+            raise ValueError(
+                "raw Conv1D specs must be [Conv1D..., Flatten, Dense] (one "
+                "Dense output layer after Flatten)"
+            )
+        if layers[-1].l1_activity:
+            raise ValueError(
+                "Unsupported activity_regularizer on the Dense layer of a "
+                "Conv1D spec: the windowed head applies none"
+            )
+        return ModelSpec(
+            model_type="conv1d",
+            n_features=n_features,
+            n_features_out=layers[-1].units,
+            layers=layers,
+            lookback_window=lookback_window,
+            loss=loss,
+            loss_kwargs=loss_kw,
+            optimizer=optimizer,
+            optimizer_kwargs=opt_kw,
+        )
     if has_gru:
         if has_lstm:
             raise ValueError(
@@ -620,6 +679,57 @@ def _parse_raw_gru(lkw: dict, n_features_out: int) -> LayerSpec:
         activation="tanh",
         return_sequences=bool(lkw.get("return_sequences", False)),
         **_raw_weight_regs("GRU", lkw),
+    )
+
+
+def _parse_raw_conv1d(lkw: dict) -> LayerSpec:
+    """A raw ``Conv1D`` layer. The engine's kernels run strides 1,
+    groups 1, channels last, with bias, ``same`` or ``causal`` padding:
+    every other setting raises here, naming the setting."""
+    def _one(key, default):
+        v = lkw.get(key, default)
+        if isinstance(v, (list, tuple)):
+            if len(v) != 1:
+                raise ValueError(f"Unsupported Conv1D {key} {v!r}")
+            v = v[0]
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"Unsupported Conv1D {key} {v!r}: not an integer")
+        return v
+
+    if "filters" not in lkw or "kernel_size" not in lkw:
+        raise ValueError("a Conv1D layer needs filters and kernel_size")
+    padding = lkw.get("padding", "valid")
+    if not (isinstance(padding, str) and padding.lower() in ("same", "causal")):
+        raise ValueError(
+            f"Unsupported Conv1D padding {padding!r}: the engine keeps the "
+            "window length, with padding 'same' or 'causal'"
+        )
+    if _one("strides", 1) != 1:
+        raise ValueError(f"Unsupported Conv1D strides {lkw['strides']!r}: "
+                         "the engine runs strides 1")
+    if _one("groups", 1) != 1:
+        raise ValueError(f"Unsupported Conv1D groups {lkw['groups']!r}: "
+                         "the engine runs groups 1")
+    if not lkw.get("use_bias", True):
+        raise ValueError("Unsupported Conv1D use_bias=False: the engine's "
+                         "kernels always add the bias")
+    if lkw.get("data_format") not in (None, "channels_last"):
+        raise ValueError(
+            f"Unsupported Conv1D data_format {lkw['data_format']!r}: the "
+            "engine's windows are channels_last"
+        )
+    if lkw.get("activity_regularizer") is not None:
+        raise ValueError("Unsupported Conv1D activity_regularizer: the "
+                         "engine applies none to Conv1D outputs")
+    return LayerSpec(
+        kind="conv1d",
+        units=_one("filters", None),
+        # None is linear, as in Keras; an unknown name raises in LayerSpec
+        activation=lkw.get("activation"),
+        kernel_size=_one("kernel_size", None),
+        dilation=_one("dilation_rate", 1),
+        padding=padding.lower(),
+        **_raw_weight_regs("Conv1D", lkw),
     )
 
 

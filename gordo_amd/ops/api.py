@@ -138,6 +138,80 @@ def last_wgrad_launch() -> dict:
     return {"family": family, "chunks": chunks, "mstep": mstep}
 
 
+# ---- grouped Conv1D (csrc/conv1d.hip): Keras Conv1D with strides 1,
+# channels last, "same" or "causal" padding, for G models at once;
+# planned by conv_plan.h's plan_conv1d(). There is no other GPU route: a
+# shape the planner refuses raises with its message.
+def _conv1d_record(family, rows, resident, lds, blocks, chunks) -> dict:
+    return {"family": family, "rows": rows, "taps_resident": bool(resident),
+            "lds_bytes": int(lds), "blocks": blocks, "chunks": chunks}
+
+
+def _conv1d_plan(entry, G, B, T, Cin, Cout, k, dilation, padding):
+    *plan, err = _require_hip().conv1d_plan(
+        str(entry), int(G), int(B), int(T), int(Cin), int(Cout), int(k),
+        int(dilation), str(padding))
+    if err:
+        return None, err
+    return _conv1d_record(*plan), None
+
+
+def conv1d_plan(entry, G, B, T, Cin, Cout, k, dilation=1, padding="same"):
+    """What a Conv1D call would launch, without touching the GPU.
+    ``entry`` is "fwd", "bwd_data" or "wgrad". The dict holds ``family``
+    (conv1d_fwd / conv1d_bwd_data / conv1d_wgrad), ``rows`` (the time
+    tile; 32 for wgrad), ``taps_resident`` (forward / bwd-data: all k
+    weight panels stay in LDS, else the two-tap ring restaged per item;
+    wgrad: one workgroup holds every tap's accumulators, else tap groups
+    on gridDim.z), ``lds_bytes``, ``blocks`` and ``chunks`` (wgrad: more
+    than one means fp32 atomics into zeroed outputs). None where the
+    planner refuses (``conv1d_refusal`` has the reason)."""
+    return _conv1d_plan(entry, G, B, T, Cin, Cout, k, dilation, padding)[0]
+
+
+def conv1d_refusal(entry, G, B, T, Cin, Cout, k, dilation=1,
+                   padding="same"):
+    """The planner's message where ``conv1d_plan`` is None, else None."""
+    return _conv1d_plan(entry, G, B, T, Cin, Cout, k, dilation, padding)[1]
+
+
+def last_conv1d_launch() -> dict:
+    """The plan of this thread's last ``conv1d_*`` launch (the fields of
+    ``conv1d_plan``); ``family`` is "" before any launch."""
+    *plan, _err = _require_hip().last_conv1d_launch()
+    return _conv1d_record(*plan)
+
+
+def conv1d_fwd(x, W, b, act="linear", padding="same", dilation=1):
+    """y [G,B,T,Cout] = act(conv1d(x [G,B,T,Cin], W [G,k,Cin,Cout]) +
+    b [G,Cout]): y[t] = act(sum_j x[t + j*d - left] @ W[j] + b) with rows
+    outside the window zero; left = (k-1)*d for ``causal`` and
+    ((k-1)*d) // 2 for ``same``."""
+    act = act_code(act)
+    if _on_gpu(x):
+        return _require_hip().conv1d_fwd(x, W, b, act, str(padding),
+                                         int(dilation))
+    return ref.conv1d_fwd(x, W, b, act, padding, dilation)
+
+
+def conv1d_bwd_data(dZ, W, padding="same", dilation=1):
+    """dX [G,B,T,Cin] of ``conv1d_fwd``'s pre-activation gradient dZ
+    (``act_l1_bwd`` applied by the caller)."""
+    if _on_gpu(dZ):
+        return _require_hip().conv1d_bwd_data(dZ, W, str(padding),
+                                              int(dilation))
+    return ref.conv1d_bwd_data(dZ, W, padding, dilation)
+
+
+def conv1d_wgrad(x, dZ, k, padding="same", dilation=1):
+    """(dW [G,k,Cin,Cout], db [G,Cout]), fp32 on the GPU."""
+    if _on_gpu(x):
+        out = _require_hip().conv1d_wgrad(x, dZ, int(k), str(padding),
+                                          int(dilation))
+        return out[0], out[1]
+    return ref.conv1d_wgrad(x, dZ, k, padding, dilation)
+
+
 def grouped_gemm_acc(A, B, C):
     if _on_gpu(A):
         return _require_hip().grouped_gemm_acc(A, B, C)

@@ -1023,6 +1023,23 @@ std::tuple<std::string, int, int, int, int64_t, int, std::string> gru_plan(
 std::tuple<std::string, int, int, int, int64_t, int> last_gru_launch();
 }  // namespace gordo_gru
 
+// grouped Conv1D entry points (conv1d.hip; planned by conv_plan.h)
+namespace gordo_conv {
+torch::Tensor conv1d_fwd(torch::Tensor x, torch::Tensor W, torch::Tensor b,
+                         int64_t act, const std::string& padding,
+                         int64_t dilation);
+torch::Tensor conv1d_bwd_data(torch::Tensor dZ, torch::Tensor W,
+                              const std::string& padding, int64_t dilation);
+std::vector<torch::Tensor> conv1d_wgrad(torch::Tensor x, torch::Tensor dZ,
+                                        int64_t k, const std::string& padding,
+                                        int64_t dilation);
+std::tuple<std::string, int, bool, int64_t, int, int, std::string> conv1d_plan(
+    const std::string& entry, int G, int B, int T, int Cin, int Cout, int k,
+    int d, const std::string& padding);
+std::tuple<std::string, int, bool, int64_t, int, int, std::string>
+last_conv1d_launch();
+}  // namespace gordo_conv
+
 // device threshold/statistics kernels (thresholds.hip: K10-K12)
 namespace gordo_thresholds {
 torch::Tensor trail_min_max(torch::Tensor X, int64_t w);
@@ -1178,6 +1195,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("last_gru_launch", &gordo_gru::last_gru_launch,
           "(family, rows, has_dx, last_only, lds_bytes, blocks) of this "
           "thread's last GRU scan launch");
+  // grouped Conv1D (strides 1, "same" / "causal"; planned by conv_plan.h)
+  mod.def("conv1d_fwd", &gordo_conv::conv1d_fwd, py::arg("x"), py::arg("W"),
+          py::arg("b"), py::arg("act"), py::arg("padding"),
+          py::arg("dilation"),
+          "y = act(conv1d(x, W) + b) per group, channels last");
+  mod.def("conv1d_bwd_data", &gordo_conv::conv1d_bwd_data, py::arg("dZ"),
+          py::arg("W"), py::arg("padding"), py::arg("dilation"),
+          "dX of conv1d_fwd's pre-activation");
+  mod.def("conv1d_wgrad", &gordo_conv::conv1d_wgrad, py::arg("x"),
+          py::arg("dZ"), py::arg("k"), py::arg("padding"),
+          py::arg("dilation"), "{dW [G,k,Cin,Cout], db [G,Cout]} fp32");
+  mod.def("conv1d_plan", &gordo_conv::conv1d_plan,
+          "(family, rows, taps_resident, lds_bytes, blocks, chunks, error) "
+          "the planner gives a Conv1D request; host only");
+  mod.def("last_conv1d_launch", &gordo_conv::last_conv1d_launch,
+          "the same tuple for this thread's last Conv1D launch");
   mod.def("grouped_linear_fwd", &grouped_linear_fwd,
           "Y = act(X@W + b) per group (MFMA)");
   mod.def("grouped_linear_bwd_data", &grouped_linear_bwd_data,

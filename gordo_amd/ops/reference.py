@@ -100,6 +100,63 @@ def grouped_linear_wgrad(
     return dW, db
 
 
+# ---- grouped Conv1D (strides 1, channels last): the CPU lane ----------
+def conv1d_left(k: int, dilation: int, padding: str) -> int:
+    """Zero rows in front of a window: the whole halo (k-1)*d for
+    ``causal``, its smaller half for ``same`` (TensorFlow's rule: the
+    remainder goes to the right, which matters for even k)."""
+    if padding not in ("same", "causal"):
+        raise ValueError(
+            f"Conv1D padding must be 'same' or 'causal', got {padding!r}"
+        )
+    halo = (int(k) - 1) * int(dilation)
+    return halo if padding == "causal" else halo // 2
+
+
+def _shift_rows(x: torch.Tensor, s: int) -> torch.Tensor:
+    """out[g,b,t] = x[g,b,t+s], zero where t+s is outside [0, T)."""
+    T = x.shape[2]
+    out = torch.zeros_like(x)
+    lo, hi = max(0, -s), min(T, T - s)
+    if hi > lo:
+        out[:, :, lo:hi] = x[:, :, lo + s:hi + s]
+    return out
+
+
+def conv1d_fwd(x, W, b, act: int, padding: str, dilation: int):
+    """y[g,b,t] = act(sum_j x[g,b,t + j*d - left] @ W[g,j] + b[g])."""
+    k, d = W.shape[1], int(dilation)
+    left = conv1d_left(k, d, padding)
+    z = b.to(x.dtype)[:, None, None, :]
+    for j in range(k):
+        z = z + torch.einsum("gbtc,gcn->gbtn", _shift_rows(x, j * d - left),
+                             W[:, j].to(x.dtype))
+    return apply_act(z, act)
+
+
+def conv1d_bwd_data(dZ, W, padding: str, dilation: int):
+    """dX[g,b,m] = sum_j dZ[g,b,m - (j*d - left)] @ W[g,j]^T."""
+    k, d = W.shape[1], int(dilation)
+    left = conv1d_left(k, d, padding)
+    dX = 0
+    for j in range(k):
+        dX = dX + torch.einsum("gbtn,gcn->gbtc",
+                               _shift_rows(dZ, left - j * d),
+                               W[:, j].to(dZ.dtype))
+    return dX
+
+
+def conv1d_wgrad(x, dZ, k: int, padding: str, dilation: int):
+    """dW[g,j] = sum_{b,m} x[g,b,m + j*d - left]^T dZ[g,b,m]; db = sum dZ."""
+    d = int(dilation)
+    left = conv1d_left(k, d, padding)
+    dW = torch.stack([
+        torch.einsum("gbtc,gbtn->gcn", _shift_rows(x, j * d - left), dZ)
+        for j in range(int(k))
+    ], dim=1)
+    return dW, dZ.sum(dim=(1, 2))
+
+
 def grouped_gemm_acc(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor):
     """C += A @ B per group, in place (the LSTM recurrent-gate GEMM
     accumulating onto the precomputed x-side gates)."""
@@ -946,6 +1003,74 @@ def grouped_linear_bwd_data_ref(dZ, W):
 def grouped_gemm_acc_ref(A, B, C0):
     """C0[g,m,n] + sum_k A[g,m,k] B[g,k,n] (C0 holds bf16 values)."""
     return _both(lambda dt: C0.to(dt) + _contract(A.to(dt), B.to(dt)))
+
+
+# Conv1D oracles: explicit sums over the taps and over the contracted
+# channel (no torch.nn.functional.conv1d, which is what
+# tests/test_conv1d_oracle.py validates them against). The only bf16
+# store of the kernels is the output itself, which the tests' bound
+# covers; ``round_bf16`` rounds both returned values there, for callers
+# that feed them on as a kernel's bf16 output.
+def _conv_taps(x, W_of_tap, shifts, dt):
+    """sum_j rows(x shifted by shifts[j]) contracted with W_of_tap(j)."""
+    G, B, T, C = x.shape
+    out = 0
+    for j, s in enumerate(shifts):
+        rows = _shift_rows(x.to(dt), s).reshape(G, B * T, C)
+        out = out + _contract(rows, W_of_tap(j).to(dt).contiguous())
+    return out.reshape(G, B, T, -1)
+
+
+def _rounded(pair, round_bf16):
+    if not round_bf16:
+        return pair
+    return tuple(t.to(torch.bfloat16).to(t.dtype) for t in pair)
+
+
+def conv1d_fwd_ref(x, W, b, act, padding, dilation, round_bf16=False):
+    """act(sum_j sum_ci x[g,b,t+j*d-left,ci] W[g,j,ci,co] + b[g,co])."""
+    act = act_code(act)
+    k, d = W.shape[1], int(dilation)
+    left = conv1d_left(k, d, padding)
+    shifts = [j * d - left for j in range(k)]
+
+    def run(dt):
+        z = _conv_taps(x, lambda j: W[:, j], shifts, dt)
+        return apply_act(z + b.to(dt)[:, None, None, :], act)
+
+    return _rounded(_both(run), round_bf16)
+
+
+def conv1d_bwd_data_ref(dZ, W, padding, dilation, round_bf16=False):
+    """dX[g,b,m,ci] = sum_j sum_co dZ[g,b,m-(j*d-left),co] W[g,j,ci,co]."""
+    k, d = W.shape[1], int(dilation)
+    left = conv1d_left(k, d, padding)
+    shifts = [left - j * d for j in range(k)]
+    return _rounded(_both(lambda dt: _conv_taps(
+        dZ, lambda j: W[:, j].transpose(1, 2), shifts, dt)), round_bf16)
+
+
+def conv1d_wgrad_ref(x, dZ, k, padding, dilation):
+    """dW[g,j,ci,co] = sum_{b,m} x[g,b,m+j*d-left,ci] dZ[g,b,m,co] and
+    db[g,co] = sum_{b,m} dZ[g,b,m,co], both fp32 kernel outputs:
+    ``((dW, db) in fp64, (dW, db) in fp32)``."""
+    d = int(dilation)
+    left = conv1d_left(k, d, padding)
+    G, B, T, Cin = x.shape
+
+    def run(dt):
+        z = dZ.to(dt).reshape(G, B * T, -1)
+        dW = torch.stack([
+            _contract(_shift_rows(x.to(dt), j * d - left)
+                      .reshape(G, B * T, Cin).transpose(1, 2).contiguous(), z)
+            for j in range(int(k))
+        ], dim=1)
+        db = torch.zeros(G, z.shape[2], dtype=dt)
+        for m in range(B * T):
+            db += z[:, m]
+        return dW, db
+
+    return _both(run)
 
 
 def act_l1_bwd_ref(dA, Y, act, l1):
