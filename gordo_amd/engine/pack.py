@@ -1055,14 +1055,43 @@ class DensePack(BasePack):
         ]
         self._logical_in = dims[0][0]
         self._logical_out = dims[-1][1]
+        dense_layers = [l for l in self.spec.layers if l.kind == "dense"]
+        # LayerNormalization layers by the index of the Dense layer they
+        # follow (the parser puts at most one after each)
+        self.ln_layers: Dict[int, Any] = {}
+        n_dense = 0
+        for layer in self.spec.layers:
+            if layer.kind == "layernorm":
+                self.ln_layers[n_dense - 1] = layer
+            n_dense += layer.kind == "dense"
         for i, (fin, fout, _act, _l1) in enumerate(self.layer_meta):
             lfin, lfout = dims[i][0], dims[i][1]
-            regs = self.spec.layers[i].weight_regs()
+            regs = dense_layers[i].weight_regs()
             self.store.declare(f"W{i}", (self.G, fin, fout),
                                logical=(self.G, lfin, lfout),
                                reg=regs["kernel"])
             self.store.declare(f"b{i}", (self.G, fout),
                                logical=(self.G, lfout), reg=regs["bias"])
+            ln = self.ln_layers.get(i)
+            if ln is None:
+                continue
+            if self.device.type == "cuda":
+                # no other GPU route: an unplanned width ends here
+                msg = ops.layer_norm_refusal("fwd", self.G, 1, fout)
+                if msg:
+                    raise ValueError(msg)
+            # gamma / beta: two ordinary trainable vectors. Their pad
+            # entries are 0 and stay 0: the kernels give pad columns
+            # y = dx = dgamma = dbeta = 0 whatever they are fed.
+            ln_regs = ln.weight_regs()
+            if ln.scale:
+                self.store.declare(f"ln{i}_gamma", (self.G, fout),
+                                   logical=(self.G, lfout),
+                                   reg=ln_regs["kernel"])
+            if ln.center:
+                self.store.declare(f"ln{i}_beta", (self.G, fout),
+                                   logical=(self.G, lfout),
+                                   reg=ln_regs["bias"])
 
     def _init_weights(self):
         for g in range(self.G):
@@ -1074,9 +1103,28 @@ class DensePack(BasePack):
                     _glorot_uniform((lfin, lfout), gen)
                 )
                 # biases stay zero
+        for i, ln in self.ln_layers.items():
+            if ln.scale:  # ones on the logical columns; beta stays zero
+                lfout = self.layer_meta_logical[i][1]
+                self.store.views[f"ln{i}_gamma"][:, :lfout] = 1.0
 
-    def forward(self, X: torch.Tensor) -> List[torch.Tensor]:
+    def _layer_norm(self, i: int, a: torch.Tensor, store_stats: bool):
+        """LayerNormalization after Dense layer i: (y, mean, rstd)."""
+        ln = self.ln_layers[i]
+        return ops.layer_norm_fwd(
+            a,
+            self.store.views[f"ln{i}_gamma"] if ln.scale else None,
+            self.store.views[f"ln{i}_beta"] if ln.center else None,
+            self.layer_meta_logical[i][1], ln.epsilon, store_stats,
+        )
+
+    def _forward(self, X: torch.Tensor, store_stats: bool):
+        """(acts, normed): ``acts[i + 1]`` is the output of Dense layer i
+        (what ``act_l1_bwd`` and a LayerNormalization backward need) and
+        ``normed[i]`` the (y, mean, rstd) of the LayerNormalization after
+        it, whose y feeds Dense layer i + 1."""
         acts = [X]
+        normed: Dict[int, tuple] = {}
         a = X
         for i, (_fin, _fout, act, _l1) in enumerate(self.layer_meta):
             a = ops.grouped_linear_fwd(
@@ -1084,6 +1132,16 @@ class DensePack(BasePack):
                 self.store.views[f"b{i}"], act,
             )
             acts.append(a)
+            if i in self.ln_layers:
+                normed[i] = self._layer_norm(i, a, store_stats)
+                a = normed[i][0]
+        return acts, normed
+
+    def forward(self, X: torch.Tensor) -> List[torch.Tensor]:
+        acts, normed = self._forward(X, False)
+        last = len(self.layer_meta) - 1
+        if last in normed:  # the last entry is the model's output
+            acts = acts + [normed[last][0]]
         return acts
 
     def predict(self, X: torch.Tensor) -> torch.Tensor:
@@ -1102,12 +1160,29 @@ class DensePack(BasePack):
 
     def train_batch(self, Xb, Tb) -> torch.Tensor:
         Xb, Tb = self._pad_io(Xb, Tb)
-        acts = self.forward(Xb)
-        loss, dA, self.last_correct = self._loss_bwd(acts[-1], Tb)
-        for i in range(len(self.layer_meta) - 1, -1, -1):
+        acts, normed = self._forward(Xb, True)
+        last = len(self.layer_meta) - 1
+        out = normed[last][0] if last in normed else acts[-1]
+        loss, dA, self.last_correct = self._loss_bwd(out, Tb)
+        for i in range(last, -1, -1):
             _fin, _fout, act, l1 = self.layer_meta[i]
+            if i in normed:
+                # dA is the gradient of the LayerNormalization output
+                ln = self.ln_layers[i]
+                _y, mean, rstd = normed[i]
+                dA, dgamma, dbeta = ops.layer_norm_bwd(
+                    dA, acts[i + 1], mean, rstd,
+                    self.store.views[f"ln{i}_gamma"] if ln.scale else None,
+                    self.layer_meta_logical[i][1], ln.center,
+                )
+                if ln.scale:
+                    self.store.gviews[f"ln{i}_gamma"].copy_(dgamma)
+                if ln.center:
+                    self.store.gviews[f"ln{i}_beta"].copy_(dbeta)
             dZ = ops.act_l1_bwd(dA, acts[i + 1], act, l1)
-            dW, db = ops.grouped_linear_wgrad(acts[i], dZ)
+            # Dense layer i read the normalised output of layer i - 1
+            x_in = normed[i - 1][0] if i - 1 in normed else acts[i]
+            dW, db = ops.grouped_linear_wgrad(x_in, dZ)
             self.store.gviews[f"W{i}"].copy_(dW)
             self.store.gviews[f"b{i}"].copy_(db)
             if i > 0:

@@ -298,7 +298,7 @@ def parse_weight_regularizer(reg_def: Any, owner: str = "regularizer"
 
 @dataclass
 class LayerSpec:
-    kind: str  # "dense" | "lstm" | "gru" | "conv1d"
+    kind: str  # "dense" | "lstm" | "gru" | "conv1d" | "layernorm"
     units: int
     activation: str = "tanh"
     l1_activity: float = 0.0  # L1 activity regularizer weight (dense)
@@ -316,6 +316,11 @@ class LayerSpec:
     kernel_size: int = 1
     dilation: int = 1
     padding: str = "same"  # "same" | "causal"
+    # layernorm only (units = the width it normalises; no activation).
+    # Its gamma / beta regularizers ride the kernel_ / bias_ pairs.
+    epsilon: float = 1e-3
+    center: bool = True
+    scale: bool = True
 
     def __post_init__(self):
         for name in _REG_FIELDS:
@@ -342,6 +347,14 @@ class LayerSpec:
                     f"Unsupported Conv1D padding {self.padding!r}: the "
                     "engine runs 'same' and 'causal'"
                 )
+        if self.kind == "layernorm":
+            self.epsilon = float(self.epsilon)
+            if not self.epsilon >= 0.0:
+                raise ValueError(
+                    "LayerNormalization epsilon must be >= 0, got "
+                    f"{self.epsilon!r}"
+                )
+            self.center, self.scale = bool(self.center), bool(self.scale)
         if self.kind not in ("lstm", "gru") and (
             self.recurrent_l1 or self.recurrent_l2
         ):
@@ -355,7 +368,7 @@ class LayerSpec:
         self.__dict__.update(state)
         for name in _REG_FIELDS:
             self.__dict__.setdefault(name, 0.0)
-        for name, default in _CONV_FIELDS:
+        for name, default in _CONV_FIELDS + _LN_FIELDS:
             self.__dict__.setdefault(name, default)
 
     def weight_regs(self) -> Dict[str, Tuple[float, float]]:
@@ -376,17 +389,22 @@ class LayerSpec:
 
 # LayerSpec fields only a conv1d layer sets, with their defaults
 _CONV_FIELDS = (("kernel_size", 1), ("dilation", 1), ("padding", "same"))
+# and those only a layernorm layer sets
+_LN_FIELDS = (("epsilon", 1e-3), ("center", True), ("scale", True))
 
 
 def _layer_dict(d: Dict[str, Any]) -> Dict[str, Any]:
     """A layer's dict without the regularizer fields when all are zero,
-    and without the conv1d fields on every other layer: such a layer's
-    dict is what it was before those fields existed."""
+    and without the conv1d / layernorm fields on every other layer: such
+    a layer's dict is what it was before those fields existed."""
     if not any(d[name] for name in _REG_FIELDS):
         for name in _REG_FIELDS:
             del d[name]
     if d["kind"] != "conv1d":
         for name, _default in _CONV_FIELDS:
+            del d[name]
+    if d["kind"] != "layernorm":
+        for name, _default in _LN_FIELDS:
             del d[name]
     return d
 
@@ -457,11 +475,14 @@ class ModelSpec:
 
     # ---- shape helpers -------------------------------------------------
     def dense_dims(self) -> List[tuple]:
-        """[(in, out, act, l1), ...] for a pure-dense spec."""
+        """[(in, out, act, l1), ...] of the Dense layers of a pure-dense
+        spec (a LayerNormalization layer between them keeps the width)."""
         assert self.model_type == "feedforward"
         dims = []
         prev = self.n_features
         for layer in self.layers:
+            if layer.kind != "dense":
+                continue
             dims.append((prev, layer.units, layer.activation, layer.l1_activity))
             prev = layer.units
         return dims
@@ -508,6 +529,8 @@ class ModelSpec:
                 # other layers' keys stay what they were
                 + (tuple(getattr(l, name) for name, _ in _CONV_FIELDS)
                    if l.kind == "conv1d" else ())
+                + (tuple(getattr(l, name) for name, _ in _LN_FIELDS)
+                   if l.kind == "layernorm" else ())
                 for l in self.layers
             ),
             self.lookback_window,

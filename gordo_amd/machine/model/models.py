@@ -482,8 +482,9 @@ def _parse_raw_spec(
     output layer, and ``[Conv1D..., Flatten, Dense]`` window models
     (the reference's raw path accepts arbitrary keras specs,
     models.py:401-460; LSTM-in-raw-spec was a round-1 gap — VERDICT
-    next-round #8). ``Dropout``/``Activation`` wrappers raise with a
-    clear message rather than being silently ignored."""
+    next-round #8). A ``LayerNormalization`` may follow any Dense
+    layer of a pure Dense stack. ``Dropout``/``Activation`` wrappers
+    raise with a clear message rather than being silently ignored."""
     if not isinstance(spec_def, dict) or len(spec_def) != 1:
         raise ValueError("raw spec must be a single-key dict (Sequential)")
     seq_key = next(iter(spec_def))
@@ -539,6 +540,14 @@ def _parse_raw_spec(
                     "a Conv1D layer after Flatten is unsupported"
                 )
             layers.append(_parse_raw_conv1d(lkw))
+        elif lname == "LayerNormalization":
+            # after an LSTM, GRU or Conv1D layer: refused below, by stack
+            if not layers or layers[-1].kind == "layernorm":
+                raise ValueError(
+                    "Unsupported LayerNormalization position: the engine "
+                    "runs it after a Dense layer of a pure Dense stack"
+                )
+            layers.append(_parse_raw_layernorm(lkw, layers[-1].units))
         elif lname == "Flatten" and has_conv:
             data_format = lkw.get("data_format")
             if data_format not in (None, "channels_last"):
@@ -554,6 +563,15 @@ def _parse_raw_spec(
     if not layers:
         raise ValueError("raw spec contains no layers")
     loss, loss_kw, optimizer, opt_kw = _parse_raw_compile(compile_def or {})
+    if (has_conv or has_lstm or has_gru) and any(
+        l.kind == "layernorm" for l in layers
+    ):
+        raise ValueError(
+            "Unsupported LayerNormalization in a "
+            + ("Conv1D" if has_conv else "GRU" if has_gru else "LSTM")
+            + " stack: the engine runs it between the Dense layers of a "
+            "pure Dense stack only"
+        )
     if has_conv:
         if has_lstm or has_gru:
             raise ValueError(
@@ -730,6 +748,63 @@ def _parse_raw_conv1d(lkw: dict) -> LayerSpec:
         dilation=_one("dilation_rate", 1),
         padding=padding.lower(),
         **_raw_weight_regs("Conv1D", lkw),
+    )
+
+
+def _parse_raw_layernorm(lkw: dict, units: int) -> LayerSpec:
+    """A raw ``LayerNormalization`` layer over the ``units`` features of
+    the Dense layer before it. The engine's kernels normalise the last
+    axis with trainable gamma (ones) and beta (zeros): every other
+    setting raises here, naming the setting."""
+    axis = lkw.get("axis", -1)
+    if isinstance(axis, (list, tuple)) and len(axis) == 1:
+        axis = axis[0]
+    if isinstance(axis, bool) or axis != -1:
+        raise ValueError(
+            f"Unsupported LayerNormalization axis {lkw['axis']!r}: the "
+            "engine normalises the last (feature) axis, written -1 or [-1]"
+        )
+    if lkw.get("rms_scaling"):
+        raise ValueError(
+            "Unsupported LayerNormalization rms_scaling=True: the engine "
+            "centres and scales by the variance"
+        )
+    for key, default in (("beta_initializer", "zeros"),
+                         ("gamma_initializer", "ones")):
+        init = lkw.get(key, default)
+        name = init.rsplit(".", 1)[-1].lower() if isinstance(init, str) else None
+        if name != default:
+            raise ValueError(
+                f"Unsupported LayerNormalization {key} {init!r}: the engine "
+                f"starts it at {default}"
+            )
+    for key in ("beta_constraint", "gamma_constraint"):
+        if lkw.get(key) is not None:
+            raise ValueError(
+                f"Unsupported LayerNormalization {key} {lkw[key]!r}: the "
+                "engine applies no constraints"
+            )
+    regs = {}
+    for role, field in (("gamma", "kernel"), ("beta", "bias")):
+        key = f"{role}_regularizer"
+        if key in lkw:
+            regs[f"{field}_l1"], regs[f"{field}_l2"] = parse_weight_regularizer(
+                lkw[key], f"LayerNormalization {key}")
+    for flag in ("center", "scale"):
+        if not isinstance(lkw.get(flag, True), bool):
+            raise ValueError(
+                f"Unsupported LayerNormalization {flag} {lkw[flag]!r}: not a "
+                "boolean"
+            )
+    eps = lkw.get("epsilon", 1e-3)
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)):
+        raise ValueError(
+            f"Unsupported LayerNormalization epsilon {eps!r}: not a number"
+        )
+    return LayerSpec(
+        kind="layernorm", units=int(units), activation="linear",
+        epsilon=float(eps), center=lkw.get("center", True),
+        scale=lkw.get("scale", True), **regs,
     )
 
 

@@ -212,6 +212,78 @@ def conv1d_wgrad(x, dZ, k, padding="same", dilation=1):
     return ref.conv1d_wgrad(x, dZ, k, padding, dilation)
 
 
+# ---- grouped LayerNormalization (csrc/layernorm.hip): Keras 3
+# LayerNormalization(axis=-1) over the real_f logical columns of a
+# [G, B, Fp] activation; planned by ln_plan.h's plan_layer_norm(). There
+# is no other GPU route: a width the planner refuses raises with its
+# message.
+def _ln_record(family, lanes, vec, chunks, blocks) -> dict:
+    return {"family": family, "lanes": lanes, "vec": bool(vec),
+            "chunks": chunks, "blocks": blocks}
+
+
+def _ln_plan(direction, G, B, Fp):
+    if direction not in ("fwd", "bwd"):
+        raise ValueError(f"direction must be 'fwd' or 'bwd', got {direction!r}")
+    *plan, err = _require_hip().layer_norm_plan(
+        direction == "fwd", int(G), int(B), int(Fp))
+    if err:
+        return None, err
+    return _ln_record(*plan), None
+
+
+def layer_norm_plan(direction, G, B, Fp):
+    """What a LayerNormalization call would launch, without touching the
+    GPU. ``direction`` is "fwd" or "bwd". The dict holds ``family``
+    (ln_fwd / ln_bwd), ``lanes`` (the lanes that own one row: the power
+    of two >= Fp / 8, 4 to 64), ``vec`` (the 16-byte arm, for aligned
+    operands), ``chunks`` (row chunks of one model: the partial
+    parameter gradients the reduce kernel sums) and ``blocks``. None
+    where the planner refuses (``layer_norm_refusal`` has the reason)."""
+    return _ln_plan(direction, G, B, Fp)[0]
+
+
+def layer_norm_refusal(direction, G, B, Fp):
+    """The planner's message where ``layer_norm_plan`` is None, else
+    None."""
+    return _ln_plan(direction, G, B, Fp)[1]
+
+
+def last_layer_norm_launch() -> dict:
+    """The plan of this thread's last ``layer_norm_*`` launch (the fields
+    of ``layer_norm_plan``, ``vec`` as the operands' alignment decided
+    it); ``family`` is "" before any launch."""
+    *plan, _err = _require_hip().last_layer_norm_launch()
+    return _ln_record(*plan)
+
+
+def layer_norm_fwd(x, gamma, beta, real_f, eps, store_stats=True):
+    """(y, mean, rstd): y [G,B,Fp] = (x - mean) rstd gamma + beta over
+    the first ``real_f`` columns (pad columns are not summed and come
+    out 0), rstd = 1/sqrt(var + eps) with the biased two-pass variance.
+    gamma / beta: fp32 [G,Fp], or None for scale / center off. Without
+    ``store_stats`` (predict, validation) mean and rstd are None and y
+    is the same bits."""
+    if _on_gpu(x):
+        y, mean, rstd = _require_hip().layer_norm_fwd(
+            x, gamma, beta, int(real_f), float(eps), bool(store_stats))
+        return (y, mean, rstd) if store_stats else (y, None, None)
+    y, mean, rstd = ref.layer_norm_fwd(x, gamma, beta, real_f, eps)
+    return (y, mean, rstd) if store_stats else (y, None, None)
+
+
+def layer_norm_bwd(dy, x, mean, rstd, gamma, real_f, center=True):
+    """(dx, dgamma, dbeta) of ``layer_norm_fwd`` from its input and saved
+    statistics; dgamma / dbeta are fp32 [G,Fp], None without gamma /
+    with ``center`` off. Bit-identical from run to run."""
+    if _on_gpu(x):
+        dx, dgamma, dbeta = _require_hip().layer_norm_bwd(
+            dy, x, mean, rstd, gamma, int(real_f), bool(center))
+        return (dx, dgamma if gamma is not None else None,
+                dbeta if center else None)
+    return ref.layer_norm_bwd(dy, x, mean, rstd, gamma, real_f, center)
+
+
 def grouped_gemm_acc(A, B, C):
     if _on_gpu(A):
         return _require_hip().grouped_gemm_acc(A, B, C)

@@ -1040,6 +1040,25 @@ std::tuple<std::string, int, bool, int64_t, int, int, std::string>
 last_conv1d_launch();
 }  // namespace gordo_conv
 
+// grouped LayerNormalization entry points (layernorm.hip; planned by
+// ln_plan.h)
+namespace gordo_ln {
+std::vector<torch::Tensor> layer_norm_fwd(torch::Tensor x,
+                                          c10::optional<torch::Tensor> gamma,
+                                          c10::optional<torch::Tensor> beta,
+                                          int64_t real_f, double eps,
+                                          bool store_stats);
+std::vector<torch::Tensor> layer_norm_bwd(torch::Tensor dy, torch::Tensor x,
+                                          torch::Tensor mean,
+                                          torch::Tensor rstd,
+                                          c10::optional<torch::Tensor> gamma,
+                                          int64_t real_f, bool center);
+std::tuple<std::string, int, bool, int, int, std::string> layer_norm_plan(
+    bool fwd, int G, int B, int Fp);
+std::tuple<std::string, int, bool, int, int, std::string>
+last_layer_norm_launch();
+}  // namespace gordo_ln
+
 // device threshold/statistics kernels (thresholds.hip: K10-K12)
 namespace gordo_thresholds {
 torch::Tensor trail_min_max(torch::Tensor X, int64_t w);
@@ -1211,6 +1230,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "the planner gives a Conv1D request; host only");
   mod.def("last_conv1d_launch", &gordo_conv::last_conv1d_launch,
           "the same tuple for this thread's last Conv1D launch");
+  // grouped LayerNormalization over the feature axis (planned by ln_plan.h)
+  mod.def("layer_norm_fwd", &gordo_ln::layer_norm_fwd, py::arg("x"),
+          py::arg("gamma"), py::arg("beta"), py::arg("real_f"),
+          py::arg("eps"), py::arg("store_stats"),
+          "{y, mean, rstd} of LayerNormalization over the real_f logical "
+          "columns; gamma / beta None: scale / center off");
+  mod.def("layer_norm_bwd", &gordo_ln::layer_norm_bwd, py::arg("dy"),
+          py::arg("x"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"),
+          py::arg("real_f"), py::arg("center"),
+          "{dx, dgamma, dbeta} of layer_norm_fwd");
+  mod.def("layer_norm_plan", &gordo_ln::layer_norm_plan,
+          "(family, lanes, vec, chunks, blocks, error) the planner gives a "
+          "LayerNormalization request; host only");
+  mod.def("last_layer_norm_launch", &gordo_ln::last_layer_norm_launch,
+          "the same tuple for this thread's last LayerNormalization launch");
   mod.def("grouped_linear_fwd", &grouped_linear_fwd,
           "Y = act(X@W + b) per group (MFMA)");
   mod.def("grouped_linear_bwd_data", &grouped_linear_bwd_data,

@@ -157,6 +157,62 @@ def conv1d_wgrad(x, dZ, k: int, padding: str, dilation: int):
     return dW, dZ.sum(dim=(1, 2))
 
 
+# ---- grouped LayerNormalization over the feature axis ------------------
+# Keras 3 LayerNormalization(axis=-1) on [G, B, Fp] with real_f logical
+# columns: pad columns are never summed, whatever they hold, and come
+# out 0. ``total(t, dim)`` is the sum the caller wants (the oracles'
+# fp32 emulation passes a running sum).
+def _ln_fwd(x, gamma, beta, real_f, eps, total):
+    xr = x[..., :real_f]
+    mu = total(xr, -1) / real_f
+    d = xr - mu.unsqueeze(-1)
+    rstd = 1.0 / torch.sqrt(total(d * d, -1) / real_f + eps)
+    y = d * rstd.unsqueeze(-1)
+    if gamma is not None:
+        y = y * gamma[:, None, :real_f]
+    if beta is not None:
+        y = y + beta[:, None, :real_f]
+    out = torch.zeros_like(x)
+    out[..., :real_f] = y
+    return out, mu, rstd
+
+
+def _ln_bwd(dy, x, mean, rstd, gamma, real_f, center, total):
+    dyr = dy[..., :real_f]
+    xhat = (x[..., :real_f] - mean.unsqueeze(-1)) * rstd.unsqueeze(-1)
+    dxhat = dyr if gamma is None else dyr * gamma[:, None, :real_f]
+    m1 = (total(dxhat, -1) / real_f).unsqueeze(-1)
+    m2 = (total(dxhat * xhat, -1) / real_f).unsqueeze(-1)
+    dx = torch.zeros_like(x)
+    dx[..., :real_f] = rstd.unsqueeze(-1) * (dxhat - m1 - xhat * m2)
+    G, Fp = x.shape[0], x.shape[-1]
+    dgamma = dbeta = None
+    if gamma is not None:
+        dgamma = torch.zeros(G, Fp, dtype=x.dtype, device=x.device)
+        dgamma[:, :real_f] = total(dyr * xhat, 1)
+    if center:
+        dbeta = torch.zeros(G, Fp, dtype=x.dtype, device=x.device)
+        dbeta[:, :real_f] = total(dyr, 1)
+    return dx, dgamma, dbeta
+
+
+def layer_norm_fwd(x, gamma, beta, real_f: int, eps: float):
+    """(y, mean [G,B], rstd [G,B]) in x's dtype; gamma / beta [G, Fp] or
+    None (scale / center off)."""
+    dt = x.dtype
+    return _ln_fwd(x, None if gamma is None else gamma.to(dt),
+                   None if beta is None else beta.to(dt),
+                   int(real_f), float(eps), torch.sum)
+
+
+def layer_norm_bwd(dy, x, mean, rstd, gamma, real_f: int, center=True):
+    """(dx, dgamma | None, dbeta | None) of ``layer_norm_fwd``."""
+    dt = x.dtype
+    return _ln_bwd(dy.to(dt), x, mean.to(dt), rstd.to(dt),
+                   None if gamma is None else gamma.to(dt), int(real_f),
+                   bool(center), torch.sum)
+
+
 def grouped_gemm_acc(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor):
     """C += A @ B per group, in place (the LSTM recurrent-gate GEMM
     accumulating onto the precomputed x-side gates)."""
@@ -1115,6 +1171,41 @@ def mse_bwd_ref(Y, T, real_n: int = -1):
         return total * inv, (2.0 * d * inv).reshape(Y.shape)
 
     return _both(run)
+
+
+def _running_sum(t, dim):
+    """Left-to-right sum along ``dim`` in t's own dtype (see
+    ``mse_bwd_ref``: the order-free worst case of a reduction tree)."""
+    import numpy as np
+
+    a = t.numpy()
+    return torch.from_numpy(
+        np.add.accumulate(a, axis=dim, dtype=a.dtype).take(-1, axis=dim).copy()
+    )
+
+
+def _opt_to(t, dt):
+    return None if t is None else t.to(dt)
+
+
+def layer_norm_fwd_ref(x, gamma, beta, real_f, eps):
+    """``((y, mean, rstd) fp64, (y, mean, rstd) fp32)`` of
+    LayerNormalization over the first ``real_f`` columns of x [G,B,Fp]
+    (two-pass biased variance; pad columns of y are 0). ``eps`` is used
+    as the fp32 value the kernel receives."""
+    eps = float(torch.tensor(eps, dtype=torch.float32))
+    return _both(lambda dt: _ln_fwd(
+        x.to(dt), _opt_to(gamma, dt), _opt_to(beta, dt), int(real_f), eps,
+        _running_sum))
+
+
+def layer_norm_bwd_ref(dy, x, mean, rstd, gamma, real_f, center=True):
+    """``((dx, dgamma, dbeta) fp64, (...) fp32)`` from the saved fp32
+    ``mean`` / ``rstd``; dgamma is None without gamma, dbeta without
+    ``center``."""
+    return _both(lambda dt: _ln_bwd(
+        dy.to(dt), x.to(dt), mean.to(dt), rstd.to(dt), _opt_to(gamma, dt),
+        int(real_f), bool(center), _running_sum))
 
 
 def _cell_act(z, act):
